@@ -13,7 +13,17 @@ scaling, 2^20 per GPU) and the ranks form ONE filter: RCCL all-gathers the
 (max, sum, sum^2) weight triple every step and the integer CDF totals plus
 the ancestor states on resample steps.
 
-Also reported:
+A plain run sets up, warms up, times the K steps and prints the result line
+with the step kernel's roofline entry (timed inside the same K steps).
+--dump-outputs DIR then writes what the timed filter holds after its last step
+(dump_outputs below).  Everything else is measured only under --full.
+--steps is the number of timed steps at any size: a filter records one history
+slot per step (88 MB at this size), so beyond 250 steps the run goes through
+successive filters over the same observation series (pf_run below).  Known
+limit: every filter's history is a fresh allocation, and the driver takes about
+3 s per 100 GB of it, outside the timed regions: 45 s for 16384 steps.
+
+Reported by every run:
   roofline     achieved HBM GB/s of the dominant kernel (k_step) from its
                algorithmic bytes (16d+16 per particle-step: on a resample
                step the log-weight is not read, and the 4-byte range mark
@@ -21,6 +31,10 @@ Also reported:
                hipEvent-timed average duration on its stream;
                traffic = PMC HBM bytes per launch from profiles/ when present;
                step_frac = the same bytes per whole step / ms_per_step / peak.
+
+Reported under --full only:
+  log_ml_error the run's log-ML estimate against the exact Kalman-filter answer
+               over the same observations (C2 only).
   cpu_baseline the CPU oracle (C restatement of Gen's PF) on a bounded sample
                of the same workload, timed on this host with the OpenMP build
                on the CPU share the GPU box gives this job (OMP_NUM_THREADS;
@@ -66,9 +80,14 @@ def parse(argv=None):
     p.add_argument("--resampler", default="systematic")
     p.add_argument("--proposal", default="default", choices=["default", "optimal"],
                    help="optimal: the LG-SSM's locally optimal proposal (a custom proposal; not the headline)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: log_ml_error against the Kalman filter, "
+                        "the CPU baselines and the GPU/CPU parity run, and the secondary configurations")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the timed filter's outputs as DIR/<name>.npy (float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and parity")
     p.add_argument("--cpu-seconds", type=float, default=1.5, help="seconds per CPU repetition (5 per baseline)")
-    p.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 / C5 measurements")
+    p.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements")
     p.add_argument("--no-history", action="store_true")
     p.add_argument("--ess-threshold", type=float, default=None, help="default N/2 (the reference's default)")
     p.add_argument("--force-multirank", action="store_true",
@@ -232,76 +251,156 @@ def set_traffic(roofline, pmc, tol=0.15):
 
 
 # --------------------------------------------------------------- PF runs
-def pf_run(gen, ctx, dist, world, a, model, particles, kernel_name, bytes_fn, loop="run"):
-    """One filter: init, warm-up steps, then the timed region over K steps
-    (barrier + device sync on both sides, max over ranks).  loop: "run" =
-    gh_pf_run (the batched loop); "cbc" = the reference caller loop, one
-    gh_pf_maybe_resample(did, ess) + gh_pf_step per step through the C ABI as
-    a Julia ccall shim issues them (test/inference/particle_filter.jl:130-137);
-    "cbc_async" = the same with the decision not asked for (NULL did / ess)."""
+DUMP_SAMPLE = 1 << 18  # particles written by --dump-outputs at the most (27 MB of float64 at d = 10)
+DUMP_BYTES = 60 << 20  # per-particle bytes written at the most (the files stay under 64 MB at any d)
+
+
+def dump_outputs(gen, st, path, rank, world):
+    """What a caller of the timed path holds after its last step, as float64
+    <name>.npy files under `path`: the particles' latent states [n, d], log
+    weights [n] and ancestor indices [n], the log-ML estimate [1], and the ESS
+    [T] and resample decision [T] of every step of this filter (the last one
+    of a run that went through several, pf_run).  A shard of more than
+    min(DUMP_SAMPLE, DUMP_BYTES / (8 (d + 3))) particles is written as a fixed
+    sample of that many (numpy seed 0, sorted; particle_index.npy holds the
+    chosen indices), which keeps the files under 64 MB.  The inputs are seeded, so two runs with the same
+    arguments write the same files."""
+    os.makedirs(path, exist_ok=True)
+    n = st.n_local
+    idx = np.arange(n)
+    keep = min(DUMP_SAMPLE, DUMP_BYTES // (8 * (st.model.d + 3)))  # index, d states, weight, ancestor
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    ess, did = st.ess_history()
+    arrays = {
+        "particle_index": idx,
+        "states": st.states()[idx],
+        "log_weights": st.log_weights[idx],
+        "parents": st.parents[idx],
+        "log_ml": np.array([gen.log_ml_estimate(st)]),
+        "ess": ess,
+        "resampled": did,
+    }
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+# steps one filter takes: its history, 88 MB per step at the C2 size, stays within
+# 256 slots (22 GB)
+MAX_FILTER_STEPS = 250
+
+
+def filter_plan(warmup, steps, cap=MAX_FILTER_STEPS):
+    """[(untimed, timed)] steps of each filter of a run.  One filter takes
+    every step while warmup + steps <= cap.  A longer run goes through filters
+    of at most cap steps each: the first warms up over min(warmup, cap) steps,
+    every later one over min(warmup, 16)."""
+    w0 = min(warmup, cap)
+    plan = [(w0, min(steps, cap - w0))]
+    left = steps - plan[0][1]
+    rewarm = min(warmup, 16)
+    while left > 0:
+        plan.append((rewarm, min(left, cap - rewarm)))
+        left -= plan[-1][1]
+    return plan
+
+
+def pf_run(gen, ctx, dist, world, a, model, particles, kernel_name, bytes_fn, loop="run", dump=None):
+    """Init, warm-up steps, then the timed region over K steps (barrier +
+    device sync on both sides, max over ranks).  Up to MAX_FILTER_STEPS steps
+    that is one filter and one timed region, as filter_plan says.  A filter
+    records its history, one slot of states and ancestors per step, so a longer
+    run would not fit in HBM: it goes through successive filters and dt is the
+    sum of their timed regions (--steps stays the number of timed steps).  Only
+    the observation series continues from one filter to the next: each filter
+    is a fresh one, started from the prior with the same seed at the
+    observation its warm-up begins with, so such a run's ms_per_step averages
+    steps 17 to 250 or so of about steps / 234 filters, not one long filter.
+    loop: "run" = gh_pf_run (the batched loop); "cbc" = the reference caller
+    loop, one gh_pf_maybe_resample(did, ess) + gh_pf_step per step through the
+    C ABI as a Julia ccall shim issues them
+    (test/inference/particle_filter.jl:130-137); "cbc_async" = the same with
+    the decision not asked for (NULL did / ess)."""
     T = a.warmup + a.steps + 1
     seed_data = 2 if isinstance(model, gen.LinearGaussianSSM) else 3
     _, ys = model.simulate(T, np.random.default_rng(seed_data))
     n_global = particles * world
     prop = gen.OptimalProposal if a.proposal == "optimal" and isinstance(model, gen.LinearGaussianSSM) else None
     init_args = (prop, (), n_global) if prop is not None else (n_global,)
-    st = gen.initialize_particle_filter(
-        model, (1,), {("chain", 1, "y"): ys[0]}, *init_args, seed=42, resampler=a.resampler,
-        record_history=not a.no_history, history_capacity=T + 2, time_kernels=0 if a.no_kernel_timing else a.time_every,
-        ctx=ctx,
-    )
-    if dist is not None:  # (the ranks' allocations and first launches take different times)
-        ctx.synchronize()
-        dist.barrier()
-    gen.run_particle_filter(st, list(ys[1 : 1 + a.warmup]), a.ess_threshold, proposal=prop)
-    ctx.synchronize()
-    st.kernel_time_ms(reset=True)
-    # the observations of the timed steps, marshalled into the C ABI's gh_obs
-    # array before the clock starts (inputs ready, as the workload's data)
-    batch = gen.prepare_observations(model, list(ys[1 + a.warmup : 1 + a.warmup + a.steps]))
 
     def barrier():
         ctx.synchronize()
         if dist is not None:
             dist.barrier()
 
-    if loop != "run":
-        import ctypes
+    plan = filter_plan(a.warmup, a.steps)
+    dt, n_res, kms_sum, kcount = 0.0, 0, 0.0, 0
+    pos = 1  # ys[pos] is the observation of the next step
+    for k, (ws, ns) in enumerate(plan):
+        first = pos - ws if k > 0 else pos  # ys[first] is this filter's first step (a later filter re-warms)
+        st = gen.initialize_particle_filter(
+            model, (1,), {("chain", 1, "y"): ys[first - 1]}, *init_args, seed=42, resampler=a.resampler,
+            record_history=not a.no_history, history_capacity=ws + ns + 3,
+            time_kernels=0 if a.no_kernel_timing else a.time_every, ctx=ctx,
+        )
+        if dist is not None:  # (the ranks' allocations and first launches take different times)
+            ctx.synchronize()
+            dist.barrier()
+        gen.run_particle_filter(st, list(ys[first : first + ws]), a.ess_threshold, proposal=prop)
+        ctx.synchronize()
+        st.kernel_time_ms(reset=True)
+        pos = first + ws
+        if ns > 0:
+            # the observations of the timed steps, marshalled into the C ABI's gh_obs
+            # array before the clock starts (inputs ready, as the workload's data)
+            batch = gen.prepare_observations(model, list(ys[pos : pos + ns]))
+            if loop != "run":
+                import ctypes
 
-        from gen_amd import _lib
+                from gen_amd import _lib
 
-        lib = _lib.load()
-        thr = float(n_global / 2 if a.ess_threshold is None else a.ess_threshold)
-        did, ess = ctypes.c_int(), ctypes.c_double()
-        pd, pe = (ctypes.byref(did), ctypes.byref(ess)) if loop == "cbc" else (None, None)
-        obs = [ctypes.byref(batch.arr[i]) for i in range(a.steps)]
-        mr_fn, step_fn, h = lib.gh_pf_maybe_resample, lib.gh_pf_step, st.h
-    barrier()
-    t0 = time.perf_counter()
-    if loop == "run":
-        gen.run_particle_filter(st, batch, a.ess_threshold, proposal=prop)
-    else:
-        for i in range(a.steps):
-            rc = mr_fn(h, thr, pd, pe) or step_fn(h, obs[i], 0)
-            if rc:
-                _lib.check(rc)
-    barrier()
-    dt = time.perf_counter() - t0
+                lib = _lib.load()
+                thr = float(n_global / 2 if a.ess_threshold is None else a.ess_threshold)
+                did, ess = ctypes.c_int(), ctypes.c_double()
+                pd, pe = (ctypes.byref(did), ctypes.byref(ess)) if loop == "cbc" else (None, None)
+                obs = [ctypes.byref(batch.arr[i]) for i in range(ns)]
+                mr_fn, step_fn, h = lib.gh_pf_maybe_resample, lib.gh_pf_step, st.h
+            barrier()
+            t0 = time.perf_counter()
+            if loop == "run":
+                gen.run_particle_filter(st, batch, a.ess_threshold, proposal=prop)
+            else:
+                for i in range(ns):
+                    rc = mr_fn(h, thr, pd, pe) or step_fn(h, obs[i], 0)
+                    if rc:
+                        _lib.check(rc)
+            barrier()
+            dt += time.perf_counter() - t0
+            pos += ns
+            ms, cnt = st.kernel_time_ms()
+            kms_sum += ms * cnt
+            kcount += cnt
+            _, did = st.ess_history()
+            n_res += int(did[ws : ws + ns].sum())  # resamples ahead of the timed steps
+        if k + 1 < len(plan):
+            st.close()
     if dist is not None:
         import torch
 
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    kms, kcount = st.kernel_time_ms()
-    ess, did = st.ess_history()
-    n_res = int(did[a.warmup : a.warmup + a.steps].sum())  # resamples ahead of the timed steps
+    kms = kms_sum / kcount if kcount else 0.0
     lml = gen.log_ml_estimate(st)
+    ys_last = ys[first - 1 : pos]  # the observations the last filter took
     bytes_pp = bytes_fn(n_res)
     achieved = bytes_pp * st.n_local / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+    if dump is not None:
+        dump_outputs(gen, st, dump, int(os.environ.get("RANK", "0")), world)
     st.close()
     return {
-        "ys": ys, "dt": dt, "n_global": n_global, "n_res": n_res, "lml": lml, "prop": prop,
+        "ys": ys, "ys_last": ys_last, "filters": len(plan), "dt": dt, "n_global": n_global, "n_res": n_res, "lml": lml, "prop": prop,
         "roofline": {
             "bound": "hbm",
             "achieved": achieved,
@@ -666,7 +765,7 @@ def main(argv=None):
         # (the pair kernel on every rank whose first particle is a multiple of 128)
         kname = "k_step_pairs<KitModel,false>" if a.particles % 128 == 0 else "k_step<KitModel,false>"
     r = pf_run(gen, ctx, dist, world, a, model, a.particles, kname,
-               lambda n_res: 16 * d + 16)
+               lambda n_res: 16 * d + 16, dump=a.dump_outputs)
     # PMC HBM bytes per step-kernel launch of the profiled configs (tools/pmc_json.py)
     pmc = None
     if a.model == "lgssm" and a.d == 10 and a.particles == 1 << 20 and r["prop"] is None:
@@ -677,8 +776,9 @@ def main(argv=None):
 
     ys, n_global, lml = r["ys"], r["n_global"], r["lml"]
     log_ml_error = None
-    if a.model == "lgssm":
-        exact = model.kalman_log_marginal(ys[: 1 + a.warmup + a.steps])
+    if a.full and a.model == "lgssm":
+        # (the observations behind lml: the whole run's while one filter took it)
+        exact = model.kalman_log_marginal(r["ys_last"])
         log_ml_error = {"reference": "Kalman filter (exact)", "exact": exact,
                         "abs": abs(lml - exact), "rel": abs(lml - exact) / abs(exact)}
     out = {
@@ -707,25 +807,38 @@ def main(argv=None):
             "transport": a.transport if world > 1 else (f"{a.transport} (forced multi-rank)" if a.force_multirank else "none"),
             "resample_steps_timed": r["n_res"],
             "log_ml": lml,
+            # filters the run went through (pf_run); log_ml is the last one's
+            "filters": r["filters"],
         },
         # log-ML error against the exact answer of the CPU reference's target
         # (Kalman filter over the same observations; C2 only).  The estimate's
         # Monte-Carlo error at this N dominates it; parity with the CPU
         # restatement of Gen's filter at equal seeds is 1e-9 (tests/).
+        # Measured under --full; null in a plain run.
         "log_ml_error": log_ml_error,
         "roofline": r["roofline"],
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = pf_cpu_baseline(model, ys, a.cpu_seconds)
         # the headline configuration itself (N = the bench's particles, every
         # step of the run, same seed and observations): GPU vs the CPU restatement
         # at least the C2 configuration's T = 100 (BASELINE.json configs[1])
-        ys_par = ys if len(ys) >= 100 else model.simulate(100, np.random.default_rng(2))[1]
+        # (a run through several filters: the first 128 observations of the last one)
+        ys_par = ys if r["filters"] == 1 else r["ys_last"][:128]
+        if len(ys_par) < 100:
+            ys_par = model.simulate(100, np.random.default_rng(2))[1]
         par = cpu_parity(model, ys_par, a.particles, a.resampler, a.proposal)
         out["cpu_baseline"]["parity"] = par
         if out["log_ml_error"] is not None:
             out["log_ml_error"]["vs_cpu_reference_same_seed"] = {"particles": par["particles"], "rel": par["rel"]}
-    if rank == 0 and world == 1 and not a.no_secondary and a.model == "lgssm":
+    if a.full and rank == 0 and world == 1 and not a.no_secondary and a.model == "lgssm":
+        clamped = None
+        if a.warmup + a.steps > MAX_FILTER_STEPS:
+            # one filter's worth at the most (several of them size their own histories)
+            w2 = min(a.warmup, MAX_FILTER_STEPS // 2)
+            clamped = {"warmup": w2, "steps": min(a.steps, MAX_FILTER_STEPS - w2),
+                       "note": f"the run's {a.warmup} + {a.steps} steps exceed one filter's {MAX_FILTER_STEPS}"}
+            a = argparse.Namespace(**{**vars(a), "warmup": w2, "steps": clamped["steps"]})
         c4 = secondary_c4(gen, ctx, a)
         out["secondary"] = {"C4": c4, "C3": secondary_c3(gen, ctx, a), "C5": secondary_c5(gen, ctx, a),
                             "slots": secondary_slots(gen, ctx, a)}
@@ -734,6 +847,8 @@ def main(argv=None):
         if a.proposal == "default":  # (world 1: both transports, whatever --transport says)
             out["secondary"]["multirank_path"] = secondary_multirank_path(gen, a, out["ms_per_step"],
                                                                           c4["ms_per_step"])
+        if clamped:
+            out["secondary"]["steps_clamped"] = clamped
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
