@@ -30,6 +30,9 @@ from .pf import (
     maybe_resample,
     maybe_resample_async,
     metropolis_hastings,
+    choice_gradients,
+    mala,
+    hmc,
     gaussian_drift,
     GaussianDriftProposal,
     mh,
@@ -54,4 +57,5 @@ __all__ = [
     "conditional_particle_filter_step", "conditional_smc", "get_particle", "initialize_conditional_particle_filter",
     "particle_gibbs", "GenHipError", "ObservationBatch", "prepare_observations", "Selection", "select",
     "metropolis_hastings", "mh", "simulate", "SimulatedTraces", "dists", "gaussian_drift", "GaussianDriftProposal",
+    "choice_gradients", "mala", "hmc",
 ]

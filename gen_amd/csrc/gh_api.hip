@@ -51,6 +51,13 @@ GH_SL_UNIT4(GH_EXTERN_TEMPLATE)
 GH_SL_UNIT5(GH_EXTERN_TEMPLATE)
 GH_SL_UNIT6(GH_EXTERN_TEMPLATE)
 GH_SL_UNIT7(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT0(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT1(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT2(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT3(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT4(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT5(GH_EXTERN_TEMPLATE)
+GH_GRAD_UNIT6(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -3828,6 +3835,149 @@ extern "C" int gh_pf_mh_drift(gh_pf* pf, uint32_t selection, const double* sd, i
     *accepted = (int64_t)h;
   }
   return GH_OK;
+}
+
+// ------------------------------------------------------- gradient moves
+// (gh_grad.h: choice_gradients, mala, hmc).  The refusals shared by the three
+// entry points, all before any launch.
+static int grad_check(const gh_pf* pf, const char* fn, uint32_t selection, int n_moves) {
+  if (n_moves < 0) return set_err(GH_E_INVAL, "%s: n_moves < 0", fn);
+  if (pf->m->family == GH_FAMILY_HMM || pf->m->family == GH_FAMILY_SLOTS)
+    return set_err(GH_E_INVAL, "%s: not lowered for this model (the gradients are closed forms of the LG-SSM, the "
+                               "nonlinear SSM and the regression)", fn);
+  if (selection == 0 || (selection & ~latent_addresses(pf->m)) != 0)
+    return set_err(GH_E_INVAL, "%s: selection 0x%x names no latent address of this step (valid: 0x%x)", fn, selection,
+                   latent_addresses(pf->m));
+  if (pf->m->family == GH_FAMILY_REGRESSION && pf->t != 1)
+    return set_err(GH_E_STATE, "%s: the regression is a static model (t = 1)", fn);
+  if (pf->resample_calls > 0) return set_err(GH_E_STATE, "%s: call after a step and before maybe_resample", fn);
+  if (pf->cond) return set_err(GH_E_STATE, "%s: the distinguished particle of a conditional filter is fixed", fn);
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "%s: not for a filter sharded over ranks", fn);
+  if ((uint64_t)pf->rejuv_moves + (uint64_t)n_moves > kRejuvMaxMoves)
+    return set_err(GH_E_INVAL, "%s: more than %u moves at one step", fn, kRejuvMaxMoves);
+  return GH_OK;
+}
+
+static RejuvArgs grad_args(gh_pf* pf, uint32_t selection, int n_moves) {
+  RejuvArgs a{};
+  const int t = pf->t;
+  if (t >= 2) {
+    a.xprev = slot_x(pf, t - 1);
+    a.anc = anc_for_step(pf, t);
+    a.res = pf->res_hist + t;
+    a.remote = pf->rows_recv;
+    a.ld_remote = pf->D + 1;
+  }
+  a.x = slot_x(pf, t);
+  a.n = pf->n;
+  a.lo = pf->lo;
+  a.seed = pf->seed;
+  a.t = (uint32_t)t;
+  a.move0 = pf->rejuv_moves;
+  a.select = selection;
+  a.n_moves = n_moves;
+  a.accepted = pf->acc_count;
+  return a;
+}
+
+// the families Grad<Model> is written for (grad_check refuses the others)
+template <class M>
+struct has_grad : std::false_type {};
+template <int D, int S>
+struct has_grad<LGModel<D, S>> : std::true_type {};
+template <>
+struct has_grad<KitModel> : std::true_type {};
+template <>
+struct has_grad<RegModel> : std::true_type {};
+
+extern "C" int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* host_values, double* host_grads) {
+  if (!pf || !host_grads) return set_err(GH_E_INVAL, "gh_pf_choice_gradients: null argument");
+  CHECK(grad_check(pf, "gh_pf_choice_gradients", selection, 0));
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  if (host_values) CHECK(gh_pf_get_states(pf, host_values));
+  const int64_t n = pf->n;
+  const int D = pf->D;
+  if (n == 0) return GH_OK;
+  DBuf d;
+  const size_t doubles = (size_t)slot_doubles(n, D);
+  CHECK(dalloc(d, sizeof(double) * doubles));
+  const RejuvArgs a = grad_args(pf, selection, 0);
+  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
+  const bool init = pf->t == 1;
+  CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+    using M = decltype(model);
+    if constexpr (has_grad<M>::value) {
+      if (init)
+        hipLaunchKernelGGL((k_choice_gradients<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                           pf->last_obs, a, d.as<double>());
+      else
+        hipLaunchKernelGGL((k_choice_gradients<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                           pf->last_obs, a, d.as<double>());
+    }
+  }));
+  HIP_TRY(hipGetLastError());
+  std::vector<double> tiled(doubles);
+  CHECK(d2h(pf, tiled.data(), d.p, sizeof(double) * doubles));
+  for (int k = 0; k < D; ++k)
+    for (int64_t i = 0; i < n; ++i) host_grads[(int64_t)k * n + i] = tiled[xidx(i, k, D)];
+  return GH_OK;
+}
+
+// mala / hmc: K launches the kernel of one model type (init: t == 1)
+template <class K>
+static int grad_move(gh_pf* pf, const char* fn, uint32_t selection, int n_moves, int64_t* accepted, K&& launch) {
+  CHECK(grad_check(pf, fn, selection, n_moves));
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  if (!pf->acc_count) HIP_TRY(hipMalloc(&pf->acc_count, sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(pf->acc_count, 0, sizeof(unsigned long long), pf->s));
+  if (n_moves > 0 && pf->n > 0) {
+    const RejuvArgs a = grad_args(pf, selection, n_moves);
+    CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+      if constexpr (has_grad<decltype(model)>::value) launch(model, p, a, pf->t == 1);
+    }));
+    HIP_TRY(hipGetLastError());
+  }
+  pf->rejuv_moves += (uint32_t)n_moves;
+  if (accepted) {
+    unsigned long long h = 0;
+    CHECK(d2h(pf, &h, pf->acc_count, sizeof h));
+    *accepted = (int64_t)h;
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_pf_mala(gh_pf* pf, uint32_t selection, double tau, int n_moves, int64_t* accepted) {
+  if (!pf) return set_err(GH_E_INVAL, "gh_pf_mala: null pf");
+  if (!(tau > 0.0 && tau < INFINITY)) return set_err(GH_E_INVAL, "gh_pf_mala: tau = %g must be finite and > 0", tau);
+  const double sd = sqrt(2.0 * tau);
+  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
+  return grad_move(pf, "gh_pf_mala", selection, n_moves, accepted,
+                   [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
+                     using M = decltype(model);
+                     if (init)
+                       hipLaunchKernelGGL((k_mala<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                                          pf->last_obs, a, tau, sd);
+                     else
+                       hipLaunchKernelGGL((k_mala<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                                          pf->last_obs, a, tau, sd);
+                   });
+}
+
+extern "C" int gh_pf_hmc(gh_pf* pf, uint32_t selection, int L, double eps, int n_moves, int64_t* accepted) {
+  if (!pf) return set_err(GH_E_INVAL, "gh_pf_hmc: null pf");
+  if (L < 1) return set_err(GH_E_INVAL, "gh_pf_hmc: L = %d leapfrog steps (at least 1)", L);
+  if (!(eps > 0.0 && eps < INFINITY)) return set_err(GH_E_INVAL, "gh_pf_hmc: eps = %g must be finite and > 0", eps);
+  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
+  return grad_move(pf, "gh_pf_hmc", selection, n_moves, accepted,
+                   [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
+                     using M = decltype(model);
+                     if (init)
+                       hipLaunchKernelGGL((k_hmc<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                                          pf->last_obs, a, L, eps);
+                     else
+                       hipLaunchKernelGGL((k_hmc<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                                          pf->last_obs, a, L, eps);
+                   });
 }
 
 extern "C" int gh_pf_get_ess_history(gh_pf* pf, int max_steps, double* ess, int32_t* did) {

@@ -11,6 +11,7 @@
 #include "gh_simulate.h"
 #include "gh_csmc.h"
 #include "gh_slots.h"
+#include "gh_grad.h"
 
 // X is `extern template` (declaration) or `template` (definition)
 #define GH_LG_KERNELS(X, D, S)                                                                               \
@@ -103,6 +104,29 @@
 #define GH_SL_UNIT5(X) GH_SLL_KERNELS(X, 7) GH_SLL_KERNELS(X, 8) GH_SLL_KERNELS(X, 9) GH_SLL_KERNELS(X, 10)
 #define GH_SL_UNIT6(X) GH_SLL_KERNELS(X, 11) GH_SLL_KERNELS(X, 12) GH_SLL_KERNELS(X, 13)
 #define GH_SL_UNIT7(X) GH_SLL_KERNELS(X, 14) GH_SLL_KERNELS(X, 15) GH_SLL_KERNELS(X, 16)
+
+// the gradient kernels (gh_grad.h): choice_gradients, mala and hmc for the
+// continuous hand-lowered families, in gh_inst_grad<k>.hip
+#define GH_GRAD_KERNELS(X, M, P)                                                                                  \
+  X __global__ void gh::k_choice_gradients<M, true>(const double*, P, gh::StepObs, gh::RejuvArgs, double*);       \
+  X __global__ void gh::k_choice_gradients<M, false>(const double*, P, gh::StepObs, gh::RejuvArgs, double*);      \
+  X __global__ void gh::k_mala<M, true>(const double*, P, gh::StepObs, gh::RejuvArgs, double, double);            \
+  X __global__ void gh::k_mala<M, false>(const double*, P, gh::StepObs, gh::RejuvArgs, double, double);           \
+  X __global__ void gh::k_hmc<M, true>(const double*, P, gh::StepObs, gh::RejuvArgs, int, double);                \
+  X __global__ void gh::k_hmc<M, false>(const double*, P, gh::StepObs, gh::RejuvArgs, int, double);
+#define GH_GRAD_LG(X, D, S) GH_GRAD_KERNELS(X, GH_GRAD_LGM(D, S), gh::LGParams)
+#define GH_GRAD_LGM(D, S) gh::LGModel<D, S>
+#define GH_GRAD_DIM(X, D) GH_GRAD_LG(X, D, 0) GH_GRAD_LG(X, D, 1) GH_GRAD_LG(X, D, 2) GH_GRAD_LG(X, D, 3)
+#define GH_GRAD_UNIT0(X)                                                                                   \
+  GH_GRAD_KERNELS(X, gh::KitModel, gh::KitParams)                                                          \
+  GH_GRAD_KERNELS(X, gh::RegModel, gh::RegParams)                                                          \
+  GH_GRAD_DIM(X, 1) GH_GRAD_DIM(X, 2) GH_GRAD_DIM(X, 3) GH_GRAD_DIM(X, 4) GH_GRAD_DIM(X, 5) GH_GRAD_DIM(X, 6)
+#define GH_GRAD_UNIT1(X) GH_GRAD_DIM(X, 7) GH_GRAD_DIM(X, 8) GH_GRAD_DIM(X, 9)
+#define GH_GRAD_UNIT2(X) GH_GRAD_DIM(X, 10) GH_GRAD_DIM(X, 11)
+#define GH_GRAD_UNIT3(X) GH_GRAD_DIM(X, 12) GH_GRAD_DIM(X, 13)
+#define GH_GRAD_UNIT4(X) GH_GRAD_DIM(X, 14)
+#define GH_GRAD_UNIT5(X) GH_GRAD_DIM(X, 15)
+#define GH_GRAD_UNIT6(X) GH_GRAD_DIM(X, 16)
 
 #define GH_EXTERN_TEMPLATE extern template
 #define GH_TEMPLATE template

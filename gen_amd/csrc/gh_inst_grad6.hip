@@ -1,0 +1,5 @@
+// gh_inst_grad6.hip — explicit instantiations of the gradient kernels (see gh_inst.h)
+#include <hip/hip_runtime.h>
+#include "gh_inst.h"
+
+GH_GRAD_UNIT6(GH_TEMPLATE)

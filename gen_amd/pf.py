@@ -748,6 +748,46 @@ def metropolis_hastings(state: ParticleFilterState, selection, *args, n_moves: i
 mh = metropolis_hastings
 
 
+def choice_gradients(state: ParticleFilterState, selection) -> tuple[np.ndarray, np.ndarray]:
+    """``choice_gradients(trace, selection)`` on every particle's trace
+    (src/gen_fn_interface.jl:374-406): the values of the current step's latent
+    and the gradient of the trace's score with respect to them, both shaped
+    like ``state.states()``.  The selection names latent addresses of the
+    current step (as ``mh``); unselected components of the regression get
+    gradient 0.  Lowered for the LG-SSM, the nonlinear SSM and the regression."""
+    mask = _latent_mask(state, selection)
+    d = state.model.d
+    values = np.empty((d, state.n_local), dtype=np.float64)
+    grads = np.empty((d, state.n_local), dtype=np.float64)
+    _lib.check(_lib.load().gh_pf_choice_gradients(state.h, mask, _lib.dptr(values), _lib.dptr(grads)))
+    return values.T.copy(), grads.T.copy()
+
+
+def mala(state: ParticleFilterState, selection, tau: float, n_moves: int = 1) -> int:
+    """``mala(trace, selection, tau)`` (src/inference/mala.jl:11-54) applied
+    n_moves times to every particle's trace: a Langevin proposal
+    normal(x + tau grad, sqrt(2 tau)) on the selected latent addresses of the
+    current step.  Log weights are unchanged.  Returns the accepted moves over
+    this rank's particles."""
+    mask = _latent_mask(state, selection)
+    acc = c_int64()
+    _lib.check(_lib.load().gh_pf_mala(state.h, mask, float(tau), int(n_moves), byref(acc)))
+    state.moves += 1
+    return int(acc.value)
+
+
+def hmc(state: ParticleFilterState, selection, L: int = 10, eps: float = 0.1, n_moves: int = 1) -> int:
+    """``hmc(trace, selection; L=10, eps=0.1)`` (src/inference/hmc.jl:25-72)
+    applied n_moves times to every particle's trace: L leapfrog steps of size
+    eps on the selected latent addresses of the current step.  Log weights are
+    unchanged.  Returns the accepted moves over this rank's particles."""
+    mask = _latent_mask(state, selection)
+    acc = c_int64()
+    _lib.check(_lib.load().gh_pf_hmc(state.h, mask, int(L), float(eps), int(n_moves), byref(acc)))
+    state.moves += 1
+    return int(acc.value)
+
+
 # ------------------------------------------------------ conditional SMC
 def _ref_state(model: Model, x) -> np.ndarray:
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.float64)).ravel())

@@ -22,6 +22,12 @@
  *                           every particle               examples/regression/quickstart.jl:17-22
  *   gh_pf_mh_drift          mh(trace, drift, (sd,)) on   src/inference/mh.jl:41-62 (proposal form)
  *                           every particle
+ *   gh_pf_choice_gradients  choice_gradients(trace,      src/gen_fn_interface.jl:374-406,
+ *                           selection) on every particle src/static_ir/backprop.jl
+ *   gh_pf_mala              mala(trace, selection, tau)  src/inference/mala.jl:11-54
+ *                           on every particle
+ *   gh_pf_hmc               hmc(trace, selection; L,     src/inference/hmc.jl:25-72
+ *                           eps) on every particle
  *   gh_pf_init_conditional /
  *   gh_pf_step_conditional  conditional_smc              examples/pmmh/smc.jl:100-151
  *   gh_is_run               importance_sampling          src/inference/importance.jl:20-52
@@ -428,6 +434,33 @@ int gh_pf_mh_select(gh_pf* pf, uint32_t selection, int n_moves, int64_t* accepte
    cancel exactly).  sd[d]: > 0 for the selected components.  Not for the
    HMM (a discrete latent).  Same calling rules and draws as gh_pf_rejuvenate. */
 int gh_pf_mh_drift(gh_pf* pf, uint32_t selection, const double* sd /* [d] */, int n_moves, int64_t* accepted);
+/* choice_gradients(trace, selection, nothing) on every particle (the GFI's
+   choice_gradients, src/gen_fn_interface.jl:374-406; the reference differentiates
+   through the trace, src/static_ir/backprop.jl): the values of the current
+   step's latent and the gradient of the trace's score with respect to them —
+   the step's latent score plus observation score, the current latent having
+   no children yet.  The gradients are closed forms of the hand-lowered
+   continuous families (LG-SSM, nonlinear SSM, regression; gh_grad.h); the HMM
+   and slot-described models are not lowered (GH_E_INVAL).  selection: bit
+   layout as gh_pf_mh_select; unselected components of the regression get
+   gradient 0.  host_values (optional) and host_grads are [d][n_local].  One
+   rank, not a conditional filter, after a step and before
+   gh_pf_maybe_resample (GH_E_STATE otherwise); the regression at t = 1. */
+int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* host_values /* [d][n_local], nullable */,
+                           double* host_grads /* [d][n_local] */);
+/* mala(trace, selection, tau) on every particle (src/inference/mala.jl:11-54):
+   propose normal(x + tau grad(x), sqrt(2 tau)) on the selected components of
+   the current latent, accept iff log(rand()) < update weight - fwd score +
+   bwd score.  tau finite and > 0.  Families, calling rules and refusals as
+   gh_pf_choice_gradients; draw windows and the per-step move counter are
+   shared with gh_pf_rejuvenate (at most 2^24 moves per step).  Log weights
+   are unchanged.  *accepted (optional, synchronises) as gh_pf_rejuvenate. */
+int gh_pf_mala(gh_pf* pf, uint32_t selection, double tau, int n_moves, int64_t* accepted);
+/* hmc(trace, selection; L, eps) on every particle (src/inference/hmc.jl:25-72):
+   standard normal momenta on the selected components, L >= 1 leapfrog steps
+   of size eps (finite, > 0), accept iff log(rand()) < new score - old score +
+   new kinetic - old kinetic.  Otherwise as gh_pf_mala. */
+int gh_pf_hmc(gh_pf* pf, uint32_t selection, int L, double eps, int n_moves, int64_t* accepted);
 /* Conditional SMC (examples/pmmh/smc.jl:100-151, the particle-Gibbs sweep):
    particle 0 is the distinguished particle, pinned to ref_x1 at init and to
    ref_xt at each step, its parent always itself, its weight the observation
