@@ -1424,6 +1424,98 @@ __device__ __forceinline__ double u52_to_f64(uint64_t q) {
   return as_f64(q + 0x4330000000000000ull) - 0x1p52;
 }
 
+// rank records and the peer transport primitives (used by the shared resample parts too)
+constexpr int kRecWords = 4;  // rank record: integer total, S_r, S2_r (f64 bits), M (f64 bits)
+// ---------------------------------------------- peer transport primitives
+// (gh_peer.h: the transport's design; gh_ctx_create_peer)
+constexpr int kAgWords = 8;  // largest small all-gather payload (u64 words)
+constexpr int kPeerMaxRanks = 64;
+constexpr double kPeerWaitDefaultS = 30.0;  // default bound of a device wait on a peer (gh_ctx_set_peer_timeout)
+
+// mailbox layout (u64 words), for R ranks
+__host__ __device__ __forceinline__ int64_t mb_sh(int R, int par, int r) { return (int64_t)par * R + r; }
+__host__ __device__ __forceinline__ int64_t mb_sh_tag(int R, int par, int r) { return 2LL * R + (int64_t)par * R + r; }
+__host__ __device__ __forceinline__ int64_t mb_rec(int R, int par, int r) {
+  return 4LL * R + ((int64_t)par * R + r) * kRecWords;
+}
+__host__ __device__ __forceinline__ int64_t mb_rec_tag(int R, int par, int r) {
+  return 4LL * R + 2LL * R * kRecWords + (int64_t)par * R + r;
+}
+__host__ __device__ __forceinline__ int64_t mb_ag(int R, int par, int r) {
+  return 6LL * R + 2LL * R * kRecWords + ((int64_t)par * R + r) * kAgWords;
+}
+__host__ __device__ __forceinline__ int64_t mb_ag_tag(int R, int par, int r) {
+  return 6LL * R + 2LL * R * kRecWords + 2LL * R * kAgWords + (int64_t)par * R + r;
+}
+__host__ __device__ __forceinline__ int64_t mb_words(int R) { return 8LL * R + 2LL * R * kRecWords + 2LL * R * kAgWords; }
+
+// every rank's mailbox, as this process maps it (peer[rank] is its own)
+struct PeerBox {
+  uint64_t* peer[kPeerMaxRanks];
+  int R, rank;
+  uint64_t wait_ticks;  // the wait bound in wall-clock ticks (gh_ctx_set_peer_timeout)
+};
+
+// Wave-level poll: lanes r < R wait until word (base + stride * r) of the own
+// mailbox reaches `want` (monotonic tags).  Returns false once `ticks` of the
+// constant-rate wall clock (s_memrealtime, 100 MHz) have passed: a backstop
+// against a rank that never comes, measured in time rather than polls (a
+// slow peer — host I/O, a first launch, descheduling — is waited for up to the
+// context's bound, 30 s by default; round 5's bound was ~2.5 s of polls).
+__device__ __forceinline__ bool peer_poll(const uint64_t* own, int64_t base, int R, uint64_t want, uint64_t ticks,
+                                          int skip = -1) {
+  const int lane = threadIdx.x & 63;
+  bool ok = lane >= R || lane == skip;
+  const uint64_t t0 = wall_clock64();
+  for (unsigned spins = 0;; ++spins) {
+    if (!ok) ok = ld_sys(own + base + lane) >= want;
+    if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
+    if ((spins & 63) == 63 && wall_clock64() - t0 > ticks) return false;
+    __builtin_amdgcn_s_sleep(2);
+  }
+}
+
+// Publish `words` u64 values (lane l holds value l; lanes < words) to slot
+// `slot` of every rank's mailbox, then the tag at `tag` behind a system-scope
+// release.  One whole wave calls it.
+__device__ __forceinline__ void peer_publish(const PeerBox& pb, int64_t slot, int64_t tag, uint64_t lane_val,
+                                             int words, uint64_t use) {
+  const int lane = threadIdx.x & 63;
+  for (int q = 0; q < pb.R; ++q)
+    if (lane < words) st_sys(pb.peer[q] + slot + lane, lane_val);
+  __threadfence_system();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane < pb.R) st_sys(pb.peer[lane] + tag, use);
+}
+
+// The decision of a multi-rank resample from the R rank records (rank order):
+// the sums share the global max, so S = sum S_r, S2 = sum S2_r; host and
+// device evaluate the same arithmetic (finish_plan needs the fire flag before
+// the device has taken it).
+GH_HD Decision decide_records(const uint64_t* recs, int R, double thr) {
+  Decision d{};
+  const double M = as_f64(recs[3]);
+  double S = 0.0, S2 = 0.0;
+  for (int q = 0; q < R; ++q) {
+    S += as_f64(recs[kRecWords * q + 1]);
+    S2 += as_f64(recs[kRecWords * q + 2]);
+  }
+  d.M = M;
+  if (!(M > -INFINITY) || M == INFINITY || M != M) {
+    d.err = 3;  // GH_E_NUMERIC
+    d.ess = NAN;
+    return d;
+  }
+  d.L = M + gh_log(S);
+  d.ess = (S * S) / S2;
+  d.fire = d.ess < thr;
+  return d;
+}
+
+}  // namespace gh
+#include "gh_resample_parts.h"
+namespace gh {
+
 template <bool MARKS, int IT, bool SUMS>
 __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resample1Args r) {
   __shared__ double smd[32];
@@ -1569,43 +1661,12 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resampl
   // sums_in_pass: the same e = exp(w - M) also feed this tile's sums
   const double qscale = as_f64((uint64_t)(r.shift + 1023) << 52);
   uint64_t q[IT];
-  uint64_t tsum = 0;
-  s1 = 0.0;
-  s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    const bool in = i0 + k < r.n;
-    const double e = in ? gh_exp_nonpos(lw[k] - Mq) : 0.0;
-    q[k] = e == e ? f64_to_u52(e * qscale) : 0;  // = quantize_weight_nonpos (e * 2^shift <= 2^52)
-    tsum += q[k];
-    if (sums) {
-      const double ee = lw[k] != lw[k] ? lw[k] : e;  // NaN poisons the statistics
-      s1 += ee;
-      s2 += ee * ee;
-    }
-  }
+  uint64_t tsum;
+  tile_quantise<IT, SUMS>(lw, i0, r.n, Mq, qscale, q, tsum, s1, s2);
   const uint64_t incl = sums ? blk16_scan<true>(tsum, &s1, &s2, smu, smd) : blk16_scan<false>(tsum, &s1, &s2, smu, smd);
-  // ---- grid barrier: each tile total (< 2^62) is published as ONE 8-byte
-  // agent-scope store tagged in bit 63 with the generation's parity, and read
-  // back with agent-scope loads until every tag matches (the payload is its
-  // own flag: no counter, no fence).  sums_in_pass: the tile sums (>= 0, so
-  // their sign bit is free) are published and polled the same way.
-  const uint64_t kTag = 1ull << 63;
-  const uint64_t par = (sgen & 1u) ? kTag : 0ull;
-  // ts1/ts2 are published on EVERY generation (0 when the sums are not in
-  // this pass), so each of the three words alternates its tag strictly and a
-  // matching tag always means this generation's value: a poller can never
-  // pair a fresh tile total with sums left over from two generations back.
-  if (threadIdx.x == kRsBlock - 1) st_sc1(&r.tsum[blockIdx.x], incl | par);
-  if (threadIdx.x == 0) {
-    st_sc1(&r.ts1[blockIdx.x], (as_u64(s1) & ~kTag) | par);
-    st_sc1(&r.ts2[blockIdx.x], (as_u64(s2) & ~kTag) | par);
-  }
-  // waves 0..7 read the tile words, 64 tiles each (grid <= 512, host-checked):
-  // one poll in flight per lane, so the kernel's register budget stays at two
-  // resident 1024-thread blocks per CU; the wave sums (integer totals in any
-  // order, the weight sums by the DPP tree) are combined by thread 0 in wave
-  // order — the same arithmetic in every block
+  // ---- grid barrier (tile_publish / tile_poll: the tagged tile words)
+  const uint64_t par = tile_parity(sgen);
+  tile_publish(r, par, incl, s1, s2);
   __shared__ uint64_t spa[8], spb[8];
   __shared__ double spg[2][8];
   __shared__ uint64_t su53;
@@ -1616,64 +1677,11 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resampl
   // (not when the host waits for the decision: the call-by-call loop with
   // maybe_resample!'s Bool asked for gets it before the marks, as without)
   const bool spec = sums && sspec && !r.hdec;  // (grid-uniform)
-  {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 8 * 64) {  // a non-polling wave draws the systematic offset's uniform meanwhile
-      const u32x4 wr = rng_block(r.seed, ~0ull, r.t, STREAM_RESAMPLE, 0);  // independent of the totals
-      su53 = u53_bits(wr.x, wr.y);
-    }
-    if (w < 8) {
-      const unsigned b = (unsigned)(w * 64 + lane);
-      const bool mine = b < gridDim.x;
-      // the totals alone while the grid publishes, then the tile sums
-      // (published with them) until their tags match too: a third of the
-      // polling traffic while lagging blocks still load their tiles (C4, 512
-      // tiles: barrier 2.2 us sooner, 39.7 -> 37.8 us per step; C2 -0.9 us)
-      uint64_t v = par, v1 = par, v2 = par;
-      bool ok = !mine, timed_out = false;  // (wave-uniform)
-      for (unsigned spins = 0;; ++spins) {  // bounded (~0.5 s): a grid that is not co-resident errors out
-        if (!ok) v = ld_sc1(&r.tsum[b]);
-        ok = ok || (v & kTag) == par;
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-        if (spins == (1u << 22)) {
-          r.dev->error = 7;  // GH_E_STATE
-          sfail = 1;
-          timed_out = true;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      ok = !mine || !sums || spec || timed_out;  // (a timed-out wave does not wait a second time)
-      for (unsigned spins = 0;; ++spins) {
-        if (!ok) {
-          v1 = ld_sc1(&r.ts1[b]);
-          v2 = ld_sc1(&r.ts2[b]);
-        }
-        ok = ok || ((v1 & kTag) == par && (v2 & kTag) == par);
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-        if (spins == (1u << 22)) {
-          r.dev->error = 7;
-          sfail = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      const uint64_t x = mine ? (v & ~kTag) : 0ull;
-      const uint64_t all = wave_sum_u64(x);
-      const uint64_t before = wave_sum_u64(b < blockIdx.x ? x : 0ull);
-      double g1 = 0.0, g2 = 0.0;
-      if (sums) {
-        g1 = wave_sum(mine ? as_f64(v1 & ~kTag) : 0.0);
-        g2 = wave_sum(mine ? as_f64(v2 & ~kTag) : 0.0);
-      }
-      if (lane == 0) {
-        spa[w] = all;
-        spb[w] = before;
-        spg[0][w] = g1;
-        spg[1][w] = g2;
-      }
-    }
+  if (threadIdx.x == 8 * 64) {  // a non-polling wave draws the systematic offset's uniform meanwhile
+    const u32x4 wr = rng_block(r.seed, ~0ull, r.t, STREAM_RESAMPLE, 0);  // independent of the totals
+    su53 = u53_bits(wr.x, wr.y);
   }
+  tile_poll<true, SUMS, true>(r, par, sums && !spec, spa, spb, spg, &sfail);
   lds_barrier();
   if (threadIdx.x == 0) {
     uint64_t all = 0, before = 0;
@@ -1696,26 +1704,12 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resampl
         posted = true;
       }
     }
-    const uint64_t N = (uint64_t)r.d.n_global;
-    sd.S = all;
-    sd.base = 0;
-    sd.local = all;
-    sd.o = scale_u53(su53, all);
-    sd.invN = r.d.inv_n;
-    sd.Qs = udiv_n(all, N, sd.invN);
-    sd.Rs = all - sd.Qs * N;
-    sd.invS = recip_est((double)all);
+    sys_constants(sd, all, 0, all, su53, (uint64_t)r.d.n_global, r.d.inv_n);
     sbase = before;
     if (blockIdx.x == 0) {
       r.dev->bar_gen = sgen;  // every block has published, so has read the old value
-      r.dev->S = sd.S;
-      r.dev->base = 0;
       r.dev->local = sd.local;
-      r.dev->o = sd.o;
-      r.dev->Qs = sd.Qs;
-      r.dev->Rs = sd.Rs;
-      r.dev->invN = sd.invN;
-      r.dev->invS = sd.invS;
+      sys_constants_mirror(r.dev, sd);
     }
   }
   lds_barrier();
@@ -1740,33 +1734,7 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resampl
   // its marks or CDF
   auto decide_late = [&]() {
     if (!spec || blockIdx.x != 0) return;  // (block-uniform)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (w < 8) {
-      const unsigned b = (unsigned)(w * 64 + lane);
-      const bool mine = b < gridDim.x;
-      uint64_t v1 = ld_sc1(&r.ts1[mine ? b : 0u]);  // (every lane: no merged values)
-      uint64_t v2 = ld_sc1(&r.ts2[mine ? b : 0u]);
-      bool ok = !mine || ((v1 & kTag) == par && (v2 & kTag) == par);
-      for (unsigned spins = 0; __builtin_amdgcn_ballot_w64(!ok) != 0; ++spins) {  // (rarely taken)
-        if (spins == (1u << 22)) {
-          r.dev->error = 7;  // GH_E_STATE
-          sfail = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        if (!ok) {
-          v1 = ld_sc1(&r.ts1[b]);
-          v2 = ld_sc1(&r.ts2[b]);
-        }
-        ok = ok || ((v1 & kTag) == par && (v2 & kTag) == par);
-      }
-      const double g1 = wave_sum(mine ? as_f64(v1 & ~kTag) : 0.0);
-      const double g2 = wave_sum(mine ? as_f64(v2 & ~kTag) : 0.0);
-      if (lane == 0) {
-        spg[0][w] = g1;
-        spg[1][w] = g2;
-      }
-    }
+    tile_poll<false, true, true>(r, par, true, spa, spb, spg, &sfail);
     lds_barrier();
     if (threadIdx.x == 0) {
       double g1 = 0.0, g2 = 0.0;
@@ -1791,64 +1759,8 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_resample1(Resampl
     if (!sfail) commit();
     return;
   }
-  const uint32_t N = (uint32_t)r.mk.n_global;  // < 2^31: 32-bit slots and groups
-  // The slot counts count(X) = ceil(v), v = (X N - o) / S, as sys_count, but
-  // v advances by q N / S per particle (one FMA on the quantised weight, exact
-  // as a double) instead of being re-derived from the 64-bit X.  Error: v_0 is
-  // within 8 N 2^-53 + 2^-53 of the exact quotient (sys_count); ns = N / S to
-  // within 6 units of 2^-53 (1/S within 2 ulp, one product), so the tile's
-  // increments q ns add at most 6 N 2^-53 (their exact sum is <= N); each FMA
-  // rounds by at most N 2^-53: |v - v*| <= (14 + IT) N 2^-53 + 2^-53 <=
-  // 31 N 2^-53 + 2^-53 for IT <= 16, a quarter of count_window(N), so ceil(v)
-  // is exact outside the window and the count is taken exactly inside it.  No
-  // clamps or edge tests: for 0 < X < S, v* lies in (-1, N); X = 0 and X = S
-  // give v* = -o/S and N - o/S, whose ceilings are 0 and N (o small: inside
-  // the window, so the exact count).
-  static_assert(IT <= 16, "the error bound of the incremental slot counts");
-  const double ns = as_f64(readfirstlane_u64(as_u64((double)N * sd.invS)));  // (uniform: SGPRs)
-  // near the integers: |fr - 1/2| >= 1/2 - w (1/2 - w is a double, so the
-  // rounding of fr - 1/2 never takes a near value out; it may take a value
-  // just outside the window in, which only costs an exact count)
-  const double hw = as_f64(readfirstlane_u64(as_u64(0.5 - count_window(N))));
-  double v = fma((double)run, (double)N, -(double)sd.o) * sd.invS;
-  auto count = [&](uint64_t X) {
-    const double fl = floor(v);
-    const double fr = v - fl;
-    int32_t j = (int32_t)fl + 1;
-    const bool near = fabs(fr - 0.5) >= hw;
-    if (near) j = sys_count_exact_call(&sd, N, X);  // (exec-masked call, skipped when no lane is near)
-    return j;
-  };
-  int32_t s_i = count(run);
-  // particle i owns the slots [s_i, e_i): a tagged mark at s_i, and the carry
-  // of every 64-slot group that starts inside the range; a lane writes up to
-  // two carries itself, a longer range (a particle with > 128 offspring) gets
-  // its carries from the whole wave (one wave-wide store loop per such
-  // particle, no block barrier)
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    run += q[k];
-    v = fma(u52_to_f64(q[k]), ns, v);
-    // (a particle past n or of zero weight leaves run, v, hence the count, unchanged)
-    const int32_t e_i = count(run);
-    const uint32_t tagged = r.mk.tag | (uint32_t)(i0 + k);
-    if (e_i > s_i) r.mk.mark[(uint32_t)s_i] = tagged;
-    const uint32_t g0 = ((uint32_t)s_i + 63u) >> 6, g1 = ((uint32_t)e_i + 63u) >> 6;  // groups g with 64 g in [s_i, e_i)
-    const bool many = g1 - g0 > 2u;
-    if (!many) {
-      if (g1 > g0) r.mk.cmark[g0] = tagged;
-      if (g1 > g0 + 1u) r.mk.cmark[g0 + 1u] = tagged;
-    }
-    uint64_t bm = __builtin_amdgcn_ballot_w64(many);
-    while (bm) {
-      const int L = __builtin_ctzll(bm);
-      bm &= bm - 1;
-      const int32_t a0 = __builtin_amdgcn_readlane((int32_t)g0, L), a1 = __builtin_amdgcn_readlane((int32_t)g1, L);
-      const uint32_t tg = r.mk.tag | (uint32_t)__builtin_amdgcn_readlane((int32_t)(i0 + k), L);
-      for (int32_t g = a0 + (threadIdx.x & 63); g < a1; g += 64) r.mk.cmark[g] = tg;
-    }
-    s_i = e_i;
-  }
+  marks_loop<IT>(&sd, r.mk, (uint32_t)r.mk.n_global, run, q, i0, AllSlots{},
+                 [](int, int64_t, int32_t, int32_t, uint64_t) {});
   decide_late();
   sums_from_lds();
   if (!sfail) commit();
@@ -1898,8 +1810,7 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_a(RankAArgs r) {
     tsum += e == e ? f64_to_u52(e * qscale) : 0;
   }
   const uint64_t tot = blk16_sum_u64(tsum, smu);
-  const uint64_t kTag = 1ull << 63;
-  const uint64_t par = (sgen & 1u) ? kTag : 0ull;
+  const uint64_t par = tile_parity(sgen);
   if (threadIdx.x == 0) {
     st_sc1(&r.tsum[blockIdx.x], tot | par);
     // (a generation that skipped these would leave them one parity behind:
@@ -1912,16 +1823,16 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_a(RankAArgs r) {
   for (int b = threadIdx.x; b < (int)gridDim.x; b += kRsBlock) {
     uint64_t v = ld_sc1(&r.tsum[b]);
     unsigned spins = 0;
-    while ((v & kTag) != par) {
+    while ((v & kTileTag) != par) {
       __builtin_amdgcn_s_sleep(1);
       v = ld_sc1(&r.tsum[b]);
       if (++spins == (1u << 22)) {
-        r.dev->error = 7;  // GH_E_STATE: not co-resident (see k_resample1)
+        r.dev->error = kErrBarrier;  // not co-resident (see tile_poll)
         failed = 1;
         break;
       }
     }
-    all += v & ~kTag;
+    all += v & ~kTileTag;
   }
   all = blk16_sum_u64(all, smu);
   if (__syncthreads_or(failed)) return;  // partial totals: publish nothing
@@ -1942,69 +1853,6 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_a(RankAArgs r) {
 // second all-gather carries; the other blocks leave after publishing.  The
 // decision is taken from the R records by k_rank_b (and by the host, the same
 // arithmetic, for the split of the next step).
-constexpr int kRecWords = 4;  // rank record: integer total, S_r, S2_r (f64 bits), M (f64 bits)
-// ---------------------------------------------- peer transport primitives
-// (gh_peer.h: the transport's design; gh_ctx_create_peer)
-constexpr int kAgWords = 8;  // largest small all-gather payload (u64 words)
-constexpr int kPeerMaxRanks = 64;
-constexpr double kPeerWaitDefaultS = 30.0;  // default bound of a device wait on a peer (gh_ctx_set_peer_timeout)
-
-// mailbox layout (u64 words), for R ranks
-__host__ __device__ __forceinline__ int64_t mb_sh(int R, int par, int r) { return (int64_t)par * R + r; }
-__host__ __device__ __forceinline__ int64_t mb_sh_tag(int R, int par, int r) { return 2LL * R + (int64_t)par * R + r; }
-__host__ __device__ __forceinline__ int64_t mb_rec(int R, int par, int r) {
-  return 4LL * R + ((int64_t)par * R + r) * kRecWords;
-}
-__host__ __device__ __forceinline__ int64_t mb_rec_tag(int R, int par, int r) {
-  return 4LL * R + 2LL * R * kRecWords + (int64_t)par * R + r;
-}
-__host__ __device__ __forceinline__ int64_t mb_ag(int R, int par, int r) {
-  return 6LL * R + 2LL * R * kRecWords + ((int64_t)par * R + r) * kAgWords;
-}
-__host__ __device__ __forceinline__ int64_t mb_ag_tag(int R, int par, int r) {
-  return 6LL * R + 2LL * R * kRecWords + 2LL * R * kAgWords + (int64_t)par * R + r;
-}
-__host__ __device__ __forceinline__ int64_t mb_words(int R) { return 8LL * R + 2LL * R * kRecWords + 2LL * R * kAgWords; }
-
-// every rank's mailbox, as this process maps it (peer[rank] is its own)
-struct PeerBox {
-  uint64_t* peer[kPeerMaxRanks];
-  int R, rank;
-  uint64_t wait_ticks;  // the wait bound in wall-clock ticks (gh_ctx_set_peer_timeout)
-};
-
-// Wave-level poll: lanes r < R wait until word (base + stride * r) of the own
-// mailbox reaches `want` (monotonic tags).  Returns false once `ticks` of the
-// constant-rate wall clock (s_memrealtime, 100 MHz) have passed: a backstop
-// against a rank that never comes, measured in time rather than polls (a
-// slow peer — host I/O, a first launch, descheduling — is waited for up to the
-// context's bound, 30 s by default; round 5's bound was ~2.5 s of polls).
-__device__ __forceinline__ bool peer_poll(const uint64_t* own, int64_t base, int R, uint64_t want, uint64_t ticks,
-                                          int skip = -1) {
-  const int lane = threadIdx.x & 63;
-  bool ok = lane >= R || lane == skip;
-  const uint64_t t0 = wall_clock64();
-  for (unsigned spins = 0;; ++spins) {
-    if (!ok) ok = ld_sys(own + base + lane) >= want;
-    if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
-    if ((spins & 63) == 63 && wall_clock64() - t0 > ticks) return false;
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
-
-// Publish `words` u64 values (lane l holds value l; lanes < words) to slot
-// `slot` of every rank's mailbox, then the tag at `tag` behind a system-scope
-// release.  One whole wave calls it.
-__device__ __forceinline__ void peer_publish(const PeerBox& pb, int64_t slot, int64_t tag, uint64_t lane_val,
-                                             int words, uint64_t use) {
-  const int lane = threadIdx.x & 63;
-  for (int q = 0; q < pb.R; ++q)
-    if (lane < words) st_sys(pb.peer[q] + slot + lane, lane_val);
-  __threadfence_system();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane < pb.R) st_sys(pb.peer[lane] + tag, use);
-}
-
 struct RankA2Args {
   const double* logw;
   int64_t n;
@@ -2099,27 +1947,16 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_rank_a2(RankA2Arg
     return;
   }
   const double qscale = as_f64((uint64_t)(r.shift + 1023) << 52);
-  uint64_t tsum = 0;
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    const bool in = i0 + k < r.n;
-    const double e = in ? gh_exp_nonpos(lw[k] - M) : 0.0;
-    tsum += e == e ? f64_to_u52(e * qscale) : 0;  // = quantize_weight (k_rank_b re-quantises the same)
-    const double ee = lw[k] != lw[k] ? lw[k] : e;  // NaN poisons the statistics
-    s1 += ee;
-    s2 += ee * ee;
-  }
+  uint64_t q[IT], tsum;  // (q is not kept: k_rank_b quantises again)
+  double s1, s2;
+  tile_quantise<IT, true>(lw, i0, r.n, M, qscale, q, tsum, s1, s2);
   const uint64_t incl = blk16_scan<true>(tsum, &s1, &s2, smu, smd);
-  const uint64_t kTag = 1ull << 63;
-  const uint64_t par = (sgen & 1u) ? kTag : 0ull;
-  if (threadIdx.x == kRsBlock - 1) st_sc1(&r.tsum[blockIdx.x], incl | par);
-  if (threadIdx.x == 0) {
-    st_sc1(&r.ts1[blockIdx.x], (as_u64(s1) & ~kTag) | par);
-    st_sc1(&r.ts2[blockIdx.x], (as_u64(s2) & ~kTag) | par);
-  }
+  const uint64_t par = tile_parity(sgen);
+  tile_publish(r, par, incl, s1, s2);
   if (blockIdx.x != 0) return;
-  // block 0: the rank totals (waves 0..7 poll 64 tiles each, as k_resample1)
+  // block 0: the rank totals (waves 0..7 poll 64 tiles each).  Not tile_poll:
+  // nothing here needs the totals ahead of the sums, so one sweep loads all
+  // three words of a tile, which no mode of tile_poll issues.
   if (w < 8) {
     const unsigned b = (unsigned)(w * 64 + lane);
     const bool mine = b < gridDim.x;
@@ -2131,7 +1968,7 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_rank_a2(RankA2Arg
         v1 = ld_sc1(&r.ts1[b]);
         v2 = ld_sc1(&r.ts2[b]);
       }
-      ok = ok || ((v & kTag) == par && (v1 & kTag) == par && (v2 & kTag) == par);
+      ok = ok || ((v & kTileTag) == par && (v1 & kTileTag) == par && (v2 & kTileTag) == par);
       if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
       if (spins == (1u << 22)) {
         fail = true;
@@ -2139,9 +1976,9 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_rank_a2(RankA2Arg
       }
       __builtin_amdgcn_s_sleep(1);
     }
-    const uint64_t all = wave_sum_u64(mine ? (v & ~kTag) : 0ull);
-    const double g1 = wave_sum(mine ? as_f64(v1 & ~kTag) : 0.0);
-    const double g2 = wave_sum(mine ? as_f64(v2 & ~kTag) : 0.0);
+    const uint64_t all = wave_sum_u64(mine ? (v & ~kTileTag) : 0ull);
+    const double g1 = wave_sum(mine ? as_f64(v1 & ~kTileTag) : 0.0);
+    const double g2 = wave_sum(mine ? as_f64(v2 & ~kTileTag) : 0.0);
     if (lane == 0) {
       spa[w] = all;
       spg[0][w] = g1;
@@ -2160,7 +1997,7 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_rank_a2(RankA2Arg
       g2 += spg[1][k];
     }
     if (sfail) {
-      r.dev->error = 7;  // GH_E_STATE: partial totals
+      r.dev->error = kErrBarrier;  // partial totals
       g1 = NAN;
     }
     r.rec[0] = all;
@@ -2182,30 +2019,6 @@ __global__ __launch_bounds__(kRsBlock, IT <= 4 ? 8 : 1) void k_rank_a2(RankA2Arg
                    lane < kRecWords ? srec[lane] : 0ull, kRecWords, r.use_rec);
     }
   }
-}
-
-// The decision of a multi-rank resample from the R rank records (rank order):
-// the sums share the global max, so S = sum S_r, S2 = sum S2_r; host and
-// device evaluate the same arithmetic (finish_plan needs the fire flag before
-// the device has taken it).
-GH_HD Decision decide_records(const uint64_t* recs, int R, double thr) {
-  Decision d{};
-  const double M = as_f64(recs[3]);
-  double S = 0.0, S2 = 0.0;
-  for (int q = 0; q < R; ++q) {
-    S += as_f64(recs[kRecWords * q + 1]);
-    S2 += as_f64(recs[kRecWords * q + 2]);
-  }
-  d.M = M;
-  if (!(M > -INFINITY) || M == INFINITY || M != M) {
-    d.err = 3;  // GH_E_NUMERIC
-    d.ess = NAN;
-    return d;
-  }
-  d.L = M + gh_log(S);
-  d.ess = (S * S) / S2;
-  d.fire = d.ess < thr;
-  return d;
 }
 
 // Phase B (after the all-gather): every block derives the global systematic
@@ -2327,7 +2140,7 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
 #pragma unroll
   for (int k = 0; k < IT; ++k) lw[k] = (i0 + k < r.n) ? r.logw[i0 + k] : 0.0;
   uint64_t before = 0;  // tile offset within the rank
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kRsBlock) before += r.tsum[b] & ~(1ull << 63);
+  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kRsBlock) before += r.tsum[b] & ~kTileTag;
   __shared__ uint64_t su53;
   if (threadIdx.x == 64) {  // another wave draws the systematic offset's uniform meanwhile (independent of the totals)
     const u32x4 w = rng_block(r.seed, ~0ull, r.t, STREAM_RESAMPLE, 0);
@@ -2339,16 +2152,7 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
   const uint64_t* recs = r.recs;
   const uint64_t* totals = r.totals;
   if (peer) {
-    if (threadIdx.x < 64) {
-      const int lane = threadIdx.x & 63, par = (int)(r.use_rec & 1);
-      const uint64_t* own = r.pb.peer[r.pb.rank];
-      const bool ok = peer_poll(own, mb_rec_tag(r.pb.R, par, 0), r.pb.R, r.use_rec, r.pb.wait_ticks);
-      if (lane < r.pb.R)
-        for (int k = 0; k < kRecWords; ++k)
-          srecs[lane * kRecWords + k] = ok ? ld_sys(own + mb_rec(r.pb.R, par, lane) + k) : (k == 3 ? as_u64(NAN) : 0ull);
-      if (!ok && lane == 0) r.dev->error = kErrPeer;  // a rank never published its record
-      if (blockIdx.x == 0 && lane < kAmaxShards) r.amax_reset[lane * kAmaxStride] = kAmaxEmpty;
-    }
+    if (threadIdx.x < 64) poll_records(r.pb, r.use_rec, srecs, r.dev, r.amax_reset);
     lds_barrier();
     recs = srecs;
     totals = srecs;
@@ -2358,15 +2162,7 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
       const Decision dec = decide_records(recs, r.R, r.d.thr);
       sfire = dec.fire;
       sMq = dec.M;
-      if (blockIdx.x == 0) {
-        r.dev->pending = 0;
-        commit_decision(r.d, dec, r.dev, 0);
-        if (r.hplan) {  // the host's copy of the records, then the tag behind a system-scope release
-          for (int w = 0; w < r.R * kRecWords; ++w) r.hplan[1 + w] = recs[w];
-          __threadfence_system();
-          __hip_atomic_store(&r.hplan[0], r.htag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      if (blockIdx.x == 0) commit_records(r.d, dec, r.dev, recs, r.R, r.hplan, r.htag);
     } else {  // k_rank_a decided
       sfire = r.dev->fire;
       sMq = r.dev->M;
@@ -2389,14 +2185,7 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
       if (k < q) base += totals[k * r.tot_stride];
       S += totals[k * r.tot_stride];
     }
-    sd.S = S;
-    sd.base = base;
-    sd.local = totals[q * r.tot_stride];
-    sd.o = scale_u53(su53, S);
-    sd.invN = r.d.inv_n;
-    sd.Qs = udiv_n(S, N, sd.invN);
-    sd.Rs = S - sd.Qs * N;
-    sd.invS = recip_est((double)S);
+    sys_constants(sd, S, base, totals[q * r.tot_stride], su53, N, r.d.inv_n);
     const int64_t own_lo = r.lo, own_hi = r.lo + r.n;
     // rows this rank sends: destination blocks in rank order (lower ranks,
     // then higher ranks), each the part of [cov_lo, cov_hi) it owns
@@ -2409,40 +2198,19 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
     sra = ca - own_lo;
     srb = cb - own_lo;
     sbase = base + before;
-    if (r.peer_rows) {  // every receiving rank's [0, ra) / [rb, n) split (its rows' layout)
-      uint64_t bk = 0;
-      for (int k = 0; k < R; ++k) {
-        const uint64_t tk = totals[k * r.tot_stride];
-        const int64_t dl = r.dlo[k], dh = r.dlo[k + 1];
-        const int64_t lo_k = sys_count_exact(&sd, N, bk), hi_k = sys_count_exact(&sd, N, bk + tk);
-        sra_all[k] = (lo_k < dl ? dl : (lo_k > dh ? dh : lo_k)) - dl;
-        srb_all[k] = (hi_k < dl ? dl : (hi_k > dh ? dh : hi_k)) - dl;
-        bk += tk;
-      }
-    }
+    if (r.peer_rows) recv_coverage(&sd, N, R, totals, r.tot_stride, r.dlo, sra_all, srb_all, nullptr);
     if (blockIdx.x == 0) {
-      r.dev->S = S;
-      r.dev->base = base;
-      r.dev->o = sd.o;
-      r.dev->Qs = sd.Qs;
-      r.dev->Rs = sd.Rs;
-      r.dev->invN = sd.invN;
-      r.dev->invS = sd.invS;
+      sys_constants_mirror(r.dev, sd);
       r.dev->ra = sra;
       r.dev->rb = srb;
     }
   }
   __syncthreads();
   const double M = sMq;
-  uint64_t qv[IT];
-  uint64_t tsum = 0;
+  uint64_t qv[IT], tsum;
+  double s1, s2;  // (no sums here: phase A took them)
   const double qscale = as_f64((uint64_t)(r.shift + 1023) << 52);
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {  // (k_rank_a2's form: the branch-free exp, 3-instruction conversion)
-    const double e = (i0 + k < r.n) ? gh_exp_nonpos(lw[k] - M) : 0.0;
-    qv[k] = e == e ? f64_to_u52(e * qscale) : 0;
-    tsum += qv[k];
-  }
+  tile_quantise<IT, false>(lw, i0, r.n, M, qscale, qv, tsum, s1, s2);
   const uint64_t incl = blk16_incl_u64(tsum, smu);
   uint64_t run = sbase + incl - tsum;
   // (32-bit slots: N < 2^31, gh_pf_init; the clamp is one v_med3_i32)
@@ -2452,62 +2220,27 @@ __global__ __launch_bounds__(kRsBlock) void k_rank_b(RankBArgs r) {
   // the weight): keep the CDF, the host regrows the buffer and k_rows_fill
   // writes every row from it (rare; the hot path only tests the flag)
   const bool spill = ssend > r.rows_cap;
-  // particle i's slots [s_i, e_i) (global) by k_resample1's incremental
-  // counts (its error bound: exact outside count_window, the exact count
-  // inside); the part this rank owns, [l0, l1) in local slots, gets a tagged
-  // mark at l0 and the carry of every 64-slot group starting inside it — a
-  // lane writes up to two carries, a longer range gets them from its whole
-  // wave (no LDS copy of the range ends, no block barrier)
-  static_assert(IT <= 16, "the error bound of the incremental slot counts");
-  const double ns = as_f64(readfirstlane_u64(as_u64((double)N32 * sd.invS)));
-  const double hw = as_f64(readfirstlane_u64(as_u64(0.5 - count_window(N32))));
-  double v = fma((double)run, (double)N32, -(double)sd.o) * sd.invS;
-  auto count = [&](uint64_t X) {
-    const double fl = floor(v);
-    const double fr = v - fl;
-    int32_t j = (int32_t)fl + 1;
-    const bool near = fabs(fr - 0.5) >= hw;
-    if (near) j = sys_count_exact_call(&sd, N32, X);  // (exec-masked call, skipped when no lane is near)
-    return j;
-  };
-  auto local = [&](int32_t sl) { return (uint32_t)(min(max(sl, own_lo), own_hi) - own_lo); };
-  int32_t s_i = count(run);
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    run += qv[k];
-    v = fma(u52_to_f64(qv[k]), ns, v);
-    const int64_t i = i0 + k;
-    // (a particle past n or of zero weight leaves run, v, hence the count, unchanged)
-    const int32_t e_i = count(run);
-    const uint32_t l0 = local(s_i), l1 = local(e_i);
-    const uint32_t tagged = r.mk.tag | (uint32_t)i;
-    if (l1 > l0) r.mk.mark[l0] = tagged;
-    const uint32_t g0 = (l0 + 63u) >> 6, g1 = (l1 + 63u) >> 6;  // local groups g with 64 g in [l0, l1)
-    const bool many = g1 - g0 > 2u;
-    if (!many) {
-      if (g1 > g0) r.mk.cmark[g0] = tagged;
-      if (g1 > g0 + 1u) r.mk.cmark[g0 + 1u] = tagged;
-    }
-    uint64_t bm = __builtin_amdgcn_ballot_w64(many);
-    while (bm) {
-      const int L = __builtin_ctzll(bm);
-      bm &= bm - 1;
-      const int32_t a0 = __builtin_amdgcn_readlane((int32_t)g0, L), a1 = __builtin_amdgcn_readlane((int32_t)g1, L);
-      const uint32_t tg = r.mk.tag | (uint32_t)__builtin_amdgcn_readlane((int32_t)i, L);
-      for (int32_t g = a0 + (threadIdx.x & 63); g < a1; g += 64) r.mk.cmark[g] = tg;
-    }
-    if (spill && i < r.n) r.C[i] = run;
-    // slots of other ranks (only a range that crosses this rank's block edge):
-    // state rows, by destination then slot
-    if (e_i > s_i && (s_i < own_lo || e_i > own_hi)) {
-      if (r.peer_rows)
-        send_rows_peer(s_i, e_i, i, own_lo, own_hi, R, N, sdst_lo, sra_all, srb_all, r.prow, r.xprev, r.D, r.lo);
-      else if (!spill)
-        send_rows(s_i, e_i, i, own_lo, own_hi, R, N, sdst_lo, sseg_lo, ssoff, r.rows_cap, r.rows, r.xprev, r.D,
-                  r.lo);
-    }
-    s_i = e_i;
-  }
+  // the marks of the slots this rank owns; a range that crosses the block's
+  // edge also has slots of other ranks: their state rows, by destination then
+  // slot
+  // (the arguments the loop body uses, read once here: SGPRs through the loop)
+  const int64_t n = r.n, lo = r.lo, rows_cap = r.rows_cap;
+  uint64_t* const C = r.C;
+  double* const rows = r.rows;
+  const double* const xprev = r.xprev;
+  const int D = r.D, peer_rows = r.peer_rows;
+  marks_loop<IT>(&sd, r.mk, N32, run, qv, i0, OwnSlots{own_lo, own_hi},
+                 [&](int, int64_t i, int32_t s_i, int32_t e_i, uint64_t run_i) {
+                   if (spill && i < n) C[i] = run_i;
+                   if (e_i > s_i && (s_i < own_lo || e_i > own_hi)) {
+                     if (peer_rows)
+                       send_rows_peer(s_i, e_i, i, own_lo, own_hi, R, N, sdst_lo, sra_all, srb_all, r.prow, xprev, D,
+                                      lo);
+                     else if (!spill)
+                       send_rows(s_i, e_i, i, own_lo, own_hi, R, N, sdst_lo, sseg_lo, ssoff, rows_cap, rows, xprev, D,
+                                 lo);
+                   }
+                 });
 }
 
 // The send rows of a resample whose rows overflowed the bounded buffer, from

@@ -1,6 +1,7 @@
 """Regenerate tools/rs_stamps.patch (the resample's phase clocks, a timing-only
 variant) from the current product sources: the clock hooks are inserted at
-stable anchors of k_resample1 and the diff against the sources is written.
+stable anchors of k_resample1 (around its calls of the shared parts) and of
+marks_loop, and the diff against the sources is written.
 
 python tools/regen_rs_stamps.py      (then: python tools/variants.py build rs_stamps)
 """
@@ -65,7 +66,8 @@ def insert(s, lo, anchor, text, after=True):
 
 def stamped_kernels(s):
     head = "template <bool MARKS, int IT, bool SUMS>\n__global__ __launch_bounds__(kRsBlock"
-    s = insert(s, 0, head, MACROS, after=False)
+    # (the macros above the shared parts: marks_loop carries the per-wave hooks)
+    s = insert(s, 0, '}  // namespace gh\n#include "gh_resample_parts.h"\n', MACROS, after=False)
     k0 = s.index(head)
     end = s.index("// ------------------------------------------------ multi-rank resample", k0)
     body = s[k0:end]
@@ -79,18 +81,27 @@ def stamped_kernels(s):
     b = insert(b, 0, "  if (threadIdx.x == 0) {\n    uint64_t all = 0, before = 0;", "  GH_RS_STAMP(3);\n",
                after=False)
     b = insert(b, b.index("GH_RS_STAMP(3)"), "  if (sfail) return;\n", "  GH_RS_EXIT_AT(3);\n  GH_RS_STAMP(4);\n")
-    b = insert(b, 0, "const uint32_t N = (uint32_t)r.mk.n_global;  // < 2^31: 32-bit slots and groups\n",
+    b = insert(b, 0, "[](int, int64_t, int32_t, int32_t, uint64_t) {});\n", "  GH_RS_STAMP(5);\n")
+    j = b.rstrip("\n").rindex("\n}")  # the kernel's closing brace
+    b = b[:j] + "\n  GH_RS_STAMP(6);" + b[j:]
+    return s[:k0] + b + s[end:]
+
+
+def stamped_parts(s):
+    """the per-wave clocks and counters of the marks phase, inside marks_loop (the
+    multi-rank kernels run them too; the tools read them after k_resample1)"""
+    k0 = s.index("__device__ __forceinline__ void marks_loop(")
+    b = s[k0:]
+    b = insert(b, 0, 'static_assert(IT <= 16, "the error bound of the incremental slot counts");\n',
                "#if defined(GH_RS_STAMPS)\n  const uint64_t wt0 = wall_clock64();\n  uint64_t wmany = 0, wcar = 0, wnear = 0;\n#endif\n")
-    b = insert(b, 0, "    if (near) j = sys_count_exact_call(&sd, N, X);",
+    b = insert(b, 0, "    if (near) j = sys_count_exact_call(sd, N, X);",
                "#if defined(GH_RS_STAMPS)\n    wnear += __builtin_popcountll(__builtin_amdgcn_ballot_w64(near));\n#endif\n",
                after=False)
     b = insert(b, 0, "uint64_t bm = __builtin_amdgcn_ballot_w64(many);\n",
                "#if defined(GH_RS_STAMPS)\n    wmany += __builtin_popcountll(bm);\n#endif\n")
     b = insert(b, 0, "a1 = __builtin_amdgcn_readlane((int32_t)g1, L);\n",
                "#if defined(GH_RS_STAMPS)\n      wcar += (uint64_t)(a1 - a0);\n#endif\n")
-    loop_end = "    s_i = e_i;\n  }\n"
-    i = b.rindex(loop_end) + len(loop_end)
-    b = b[:i] + '''#if defined(GH_RS_STAMPS)
+    b = insert(b, 0, "    s_i = e_i;\n  }\n", '''#if defined(GH_RS_STAMPS)
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) {
     uint64_t* wp = g_rs_wave + ((uint64_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 4;
     wp[0] = wt0;
@@ -99,16 +110,13 @@ def stamped_kernels(s):
     wp[3] = wcar;
   }
 #endif
-  GH_RS_STAMP(5);
-''' + b[i:]
-    j = b.rstrip("\n").rindex("\n}")  # the kernel's closing brace
-    b = b[:j] + "\n  GH_RS_STAMP(6);" + b[j:]
-    return s[:k0] + b + s[end:]
+''')
+    return s[:k0] + b
 
 
 def main():
     out = []
-    for name, fn in (("gh_kernels.h", stamped_kernels),
+    for name, fn in (("gh_kernels.h", stamped_kernels), ("gh_resample_parts.h", stamped_parts),
                      ("gh_api.hip", lambda s: insert(s, 0, "// ------------------------------------------------------------------ PMMH",
                                                      API, after=False))):
         src = open(os.path.join(CSRC, name)).read()
