@@ -33,6 +33,8 @@ from .pf import (
     choice_gradients,
     mala,
     hmc,
+    elliptical_slice,
+    map_optimize,
     gaussian_drift,
     GaussianDriftProposal,
     mh,
@@ -57,5 +59,5 @@ __all__ = [
     "conditional_particle_filter_step", "conditional_smc", "get_particle", "initialize_conditional_particle_filter",
     "particle_gibbs", "GenHipError", "ObservationBatch", "prepare_observations", "Selection", "select",
     "metropolis_hastings", "mh", "simulate", "SimulatedTraces", "dists", "gaussian_drift", "GaussianDriftProposal",
-    "choice_gradients", "mala", "hmc",
+    "choice_gradients", "mala", "hmc", "elliptical_slice", "map_optimize",
 ]

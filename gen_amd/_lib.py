@@ -108,6 +108,8 @@ SIGNATURES = {
     "gh_pf_choice_gradients": (c_int, [c_void_p, ctypes.c_uint32, POINTER(c_double), POINTER(c_double)]),
     "gh_pf_mala": (c_int, [c_void_p, ctypes.c_uint32, c_double, c_int, POINTER(c_int64)]),
     "gh_pf_hmc": (c_int, [c_void_p, ctypes.c_uint32, c_int, c_double, c_int, POINTER(c_int64)]),
+    "gh_pf_elliptical_slice": (c_int, [c_void_p, ctypes.c_uint32, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "gh_pf_map_optimize": (c_int, [c_void_p, ctypes.c_uint32, c_double, c_double, c_double, c_int, POINTER(c_int64)]),
     "gh_pf_get_scores": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "gh_debug_mark_bits": (c_int, [c_void_p, c_int]),
     "gh_debug_count_window": (c_int, [c_void_p, c_int]),

@@ -58,6 +58,13 @@ GH_GRAD_UNIT3(GH_EXTERN_TEMPLATE)
 GH_GRAD_UNIT4(GH_EXTERN_TEMPLATE)
 GH_GRAD_UNIT5(GH_EXTERN_TEMPLATE)
 GH_GRAD_UNIT6(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT0(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT1(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT2(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT3(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT4(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT5(GH_EXTERN_TEMPLATE)
+GH_SLICE_UNIT6(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1329,6 +1336,7 @@ struct gh_pf {
   std::vector<std::vector<double>> raw_obs;  // every step's observation as given (index t-1; empty: none)
   uint32_t rejuv_moves = 0;
   unsigned long long* acc_count = nullptr;
+  unsigned long long* exh_count = nullptr;  // elliptical_slice: moves that ran into the shrink cap
   // the Gaussian custom proposal's last arguments (alpha, beta, gamma, sigma_q)
   double qargs[4] = {0, 0, 0, 0};
   bool has_q = false;
@@ -1509,7 +1517,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->ess_hist); hipFree(pf->res_hist); hipFree(pf->anc_scratch);
   hipFree(pf->rows_recv); hipFree(pf->rows_send); hipFree(pf->xanc); hipFree(pf->gparent);
   hipFree(pf->mn_key); hipFree(pf->mn_pos); hipFree(pf->mn_anc); hipFree(pf->mn_bcnt); hipFree(pf->mn_boff);
-  hipFree(pf->acc_count); hipFree(pf->pin); hipFree(pf->amax);
+  hipFree(pf->acc_count); hipFree(pf->exh_count); hipFree(pf->pin); hipFree(pf->amax);
   hipFree(pf->amax_all); hipFree(pf->rec); hipFree(pf->recs_all); hipFree(pf->qlin);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
@@ -3923,10 +3931,13 @@ extern "C" int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* hos
   return GH_OK;
 }
 
-// mala / hmc: K launches the kernel of one model type (init: t == 1)
+// mala / hmc / elliptical_slice / map_optimize: K launches the kernel of one
+// model type (init: t == 1).  draws: the moves consume draw windows (the
+// step's move counter advances); map_optimize draws nothing.
 template <class K>
-static int grad_move(gh_pf* pf, const char* fn, uint32_t selection, int n_moves, int64_t* accepted, K&& launch) {
-  CHECK(grad_check(pf, fn, selection, n_moves));
+static int grad_move(gh_pf* pf, const char* fn, uint32_t selection, int n_moves, int64_t* accepted, K&& launch,
+                     bool draws = true) {
+  CHECK(grad_check(pf, fn, selection, draws ? n_moves : 0));
   HIP_TRY(hipSetDevice(pf->ctx->device));
   if (!pf->acc_count) HIP_TRY(hipMalloc(&pf->acc_count, sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(pf->acc_count, 0, sizeof(unsigned long long), pf->s));
@@ -3937,7 +3948,7 @@ static int grad_move(gh_pf* pf, const char* fn, uint32_t selection, int n_moves,
     }));
     HIP_TRY(hipGetLastError());
   }
-  pf->rejuv_moves += (uint32_t)n_moves;
+  if (draws) pf->rejuv_moves += (uint32_t)n_moves;
   if (accepted) {
     unsigned long long h = 0;
     CHECK(d2h(pf, &h, pf->acc_count, sizeof h));
@@ -3978,6 +3989,66 @@ extern "C" int gh_pf_hmc(gh_pf* pf, uint32_t selection, int L, double eps, int n
                        hipLaunchKernelGGL((k_hmc<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
                                           pf->last_obs, a, L, eps);
                    });
+}
+
+// ------------------------------------ elliptical slice, map_optimize
+// (gh_slice.h).  The refusals are grad_check's, all before any launch.
+extern "C" int gh_pf_elliptical_slice(gh_pf* pf, uint32_t selection, int n_moves, int64_t* shrinks,
+                                      int64_t* exhausted) {
+  static const char* fn = "gh_pf_elliptical_slice";
+  if (!pf) return set_err(GH_E_INVAL, "gh_pf_elliptical_slice: null pf");
+  CHECK(grad_check(pf, fn, selection, n_moves));
+  if (pf->m->family == GH_FAMILY_REGRESSION && selection == latent_addresses(pf->m))
+    return set_err(GH_E_INVAL, "%s: selection 0x%x names both addresses; the slice moves one address", fn, selection);
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  if (!pf->exh_count) HIP_TRY(hipMalloc(&pf->exh_count, sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(pf->exh_count, 0, sizeof(unsigned long long), pf->s));
+  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
+  CHECK(grad_move(pf, fn, selection, n_moves, shrinks, [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
+    using M = decltype(model);
+    if (init)
+      hipLaunchKernelGGL((k_elliptical_slice<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                         pf->last_obs, a, pf->exh_count);
+    else
+      hipLaunchKernelGGL((k_elliptical_slice<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                         pf->last_obs, a, pf->exh_count);
+  }));
+  if (exhausted) {
+    unsigned long long h = 0;
+    CHECK(d2h(pf, &h, pf->exh_count, sizeof h));
+    *exhausted = (int64_t)h;
+  }
+  return GH_OK;
+}
+
+extern "C" int gh_pf_map_optimize(gh_pf* pf, uint32_t selection, double max_step_size, double tau,
+                                  double min_step_size, int n_iters, int64_t* improved) {
+  static const char* fn = "gh_pf_map_optimize";
+  if (!pf) return set_err(GH_E_INVAL, "gh_pf_map_optimize: null pf");
+  if (n_iters < 0) return set_err(GH_E_INVAL, "%s: n_iters < 0", fn);
+  if (!(max_step_size > 0.0 && max_step_size < INFINITY))
+    return set_err(GH_E_INVAL, "%s: max_step_size = %g must be finite and > 0", fn, max_step_size);
+  if (!(min_step_size > 0.0 && min_step_size < INFINITY))
+    return set_err(GH_E_INVAL, "%s: min_step_size = %g must be finite and > 0", fn, min_step_size);
+  if (!(tau > 0.0 && tau < 1.0)) return set_err(GH_E_INVAL, "%s: tau = %g must lie in (0, 1)", fn, tau);
+  // evaluations of one iteration: the step sizes max, max tau, ... down to the first below min
+  const double halvings = ceil((log(min_step_size) - log(max_step_size)) / log(tau)) + 2.0;
+  if (!(halvings <= (double)kMapMaxBacktracks))
+    return set_err(GH_E_INVAL, "%s: %g backtracking steps from %g down to %g by tau = %g (at most %d)", fn, halvings,
+                   max_step_size, min_step_size, tau, kMapMaxBacktracks);
+  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
+  return grad_move(
+      pf, fn, selection, n_iters, improved,
+      [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
+        using M = decltype(model);
+        if (init)
+          hipLaunchKernelGGL((k_map_optimize<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                             pf->last_obs, a, max_step_size, tau, min_step_size);
+        else
+          hipLaunchKernelGGL((k_map_optimize<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
+                             pf->last_obs, a, max_step_size, tau, min_step_size);
+      },
+      false);
 }
 
 extern "C" int gh_pf_get_ess_history(gh_pf* pf, int max_steps, double* ess, int32_t* did) {

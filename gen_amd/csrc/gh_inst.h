@@ -12,6 +12,7 @@
 #include "gh_csmc.h"
 #include "gh_slots.h"
 #include "gh_grad.h"
+#include "gh_slice.h"
 
 // X is `extern template` (declaration) or `template` (definition)
 #define GH_LG_KERNELS(X, D, S)                                                                               \
@@ -127,6 +128,30 @@
 #define GH_GRAD_UNIT4(X) GH_GRAD_DIM(X, 14)
 #define GH_GRAD_UNIT5(X) GH_GRAD_DIM(X, 15)
 #define GH_GRAD_UNIT6(X) GH_GRAD_DIM(X, 16)
+
+// the slice and map_optimize kernels (gh_slice.h) for the same families, in
+// gh_inst_slice<k>.hip
+#define GH_SLICE_KERNELS(X, M, P)                                                                                 \
+  X __global__ void gh::k_elliptical_slice<M, true>(const double*, P, gh::StepObs, gh::RejuvArgs,                 \
+                                                    unsigned long long*);                                         \
+  X __global__ void gh::k_elliptical_slice<M, false>(const double*, P, gh::StepObs, gh::RejuvArgs,                \
+                                                     unsigned long long*);                                        \
+  X __global__ void gh::k_map_optimize<M, true>(const double*, P, gh::StepObs, gh::RejuvArgs, double, double,     \
+                                                double);                                                          \
+  X __global__ void gh::k_map_optimize<M, false>(const double*, P, gh::StepObs, gh::RejuvArgs, double, double,    \
+                                                 double);
+#define GH_SLICE_LG(X, D, S) GH_SLICE_KERNELS(X, GH_GRAD_LGM(D, S), gh::LGParams)
+#define GH_SLICE_DIM(X, D) GH_SLICE_LG(X, D, 0) GH_SLICE_LG(X, D, 1) GH_SLICE_LG(X, D, 2) GH_SLICE_LG(X, D, 3)
+#define GH_SLICE_UNIT0(X)                                                                                  \
+  GH_SLICE_KERNELS(X, gh::KitModel, gh::KitParams)                                                         \
+  GH_SLICE_KERNELS(X, gh::RegModel, gh::RegParams)                                                         \
+  GH_SLICE_DIM(X, 1) GH_SLICE_DIM(X, 2) GH_SLICE_DIM(X, 3) GH_SLICE_DIM(X, 4) GH_SLICE_DIM(X, 5) GH_SLICE_DIM(X, 6)
+#define GH_SLICE_UNIT1(X) GH_SLICE_DIM(X, 7) GH_SLICE_DIM(X, 8) GH_SLICE_DIM(X, 9)
+#define GH_SLICE_UNIT2(X) GH_SLICE_DIM(X, 10) GH_SLICE_DIM(X, 11)
+#define GH_SLICE_UNIT3(X) GH_SLICE_DIM(X, 12) GH_SLICE_DIM(X, 13)
+#define GH_SLICE_UNIT4(X) GH_SLICE_DIM(X, 14)
+#define GH_SLICE_UNIT5(X) GH_SLICE_DIM(X, 15)
+#define GH_SLICE_UNIT6(X) GH_SLICE_DIM(X, 16)
 
 #define GH_EXTERN_TEMPLATE extern template
 #define GH_TEMPLATE template

@@ -1,0 +1,5 @@
+// gh_inst_slice6.hip — explicit instantiations of the slice and map_optimize kernels (see gh_inst.h)
+#include <hip/hip_runtime.h>
+#include "gh_inst.h"
+
+GH_SLICE_UNIT6(GH_TEMPLATE)

@@ -788,6 +788,51 @@ def hmc(state: ParticleFilterState, selection, L: int = 10, eps: float = 0.1, n_
     return int(acc.value)
 
 
+def elliptical_slice(state: ParticleFilterState, selection, n_moves: int = 1) -> tuple[int, int]:
+    """``elliptical_slice(trace, addr, mu, cov)``
+    (src/inference/elliptical_slice.jl:13-45) applied n_moves times to every
+    particle's trace: the selected latent address of the current step moves on
+    the ellipse through its value and a draw from its prior, the angle
+    shrinking until the slice test passes.  No step size and no rejection.
+
+    ``mu`` and ``cov`` are the model's own prior of the address given the
+    particle's parent (the transition density, or the initial one at t = 1;
+    the regression's normal prior of "slope" or of "intercept"), which is why
+    they are not arguments.  The selection names one address.
+
+    The slice is on the likelihood only (Murray, Adams, MacKay 2010): accept
+    iff loglik(x') - loglik(x) > log u.  The reference slices on the whole
+    update weight, which counts the moved address's prior twice; that is not
+    reproduced.
+
+    Log weights are unchanged.  Returns (shrinks, exhausted) over this rank's
+    particles: the shrink steps taken, and the moves that used all 64 allowed
+    shrinks and left their particle where it was."""
+    mask = _latent_mask(state, selection)
+    shr, exh = c_int64(), c_int64()
+    _lib.check(_lib.load().gh_pf_elliptical_slice(state.h, mask, int(n_moves), byref(shr), byref(exh)))
+    state.moves += 1
+    return int(shr.value), int(exh.value)
+
+
+def map_optimize(state: ParticleFilterState, selection, max_step_size: float = 0.1, tau: float = 0.5,
+                 min_step_size: float = 1e-16, n_iters: int = 1) -> int:
+    """``map_optimize(trace, selection; max_step_size=0.1, tau=0.5,
+    min_step_size=1e-16)`` (src/inference/map_optimize.jl:9-41) applied
+    n_iters times to every particle's trace: backtracking gradient ascent on
+    the trace's score over the selected latent addresses of the current step.
+    Each iteration tries x + step * gradient from step = max_step_size and
+    multiplies step by tau while the score got worse; it keeps x once step <
+    min_step_size.  Draws nothing.  Log weights are unchanged.  Returns the
+    iterations that improved, over this rank's particles."""
+    mask = _latent_mask(state, selection)
+    imp = c_int64()
+    _lib.check(_lib.load().gh_pf_map_optimize(state.h, mask, float(max_step_size), float(tau), float(min_step_size),
+                                              int(n_iters), byref(imp)))
+    state.moves += 1
+    return int(imp.value)
+
+
 # ------------------------------------------------------ conditional SMC
 def _ref_state(model: Model, x) -> np.ndarray:
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.float64)).ravel())

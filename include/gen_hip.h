@@ -28,6 +28,10 @@
  *                           on every particle
  *   gh_pf_hmc               hmc(trace, selection; L,     src/inference/hmc.jl:25-72
  *                           eps) on every particle
+ *   gh_pf_elliptical_slice  elliptical_slice(trace, addr, src/inference/elliptical_slice.jl:13-45
+ *                           mu, cov) on every particle   (the likelihood-only slice, see below)
+ *   gh_pf_map_optimize      map_optimize(trace,          src/inference/map_optimize.jl:9-41
+ *                           selection) on every particle
  *   gh_pf_init_conditional /
  *   gh_pf_step_conditional  conditional_smc              examples/pmmh/smc.jl:100-151
  *   gh_is_run               importance_sampling          src/inference/importance.jl:20-52
@@ -461,6 +465,37 @@ int gh_pf_mala(gh_pf* pf, uint32_t selection, double tau, int n_moves, int64_t* 
    of size eps (finite, > 0), accept iff log(rand()) < new score - old score +
    new kinetic - old kinetic.  Otherwise as gh_pf_mala. */
 int gh_pf_hmc(gh_pf* pf, uint32_t selection, int L, double eps, int n_moves, int64_t* accepted);
+/* elliptical_slice(trace, addr, mu, cov) on every particle
+   (src/inference/elliptical_slice.jl:13-45; Murray, Adams, MacKay 2010): the
+   selected latent address of the current step moves on the ellipse through
+   its value and a fresh draw nu ~ N(0, cov), the angle shrinking towards the
+   current value until the slice test passes.  mu and cov are the model's own
+   prior of the address given the particle's parent, hence no arguments.  The
+   slice is on the likelihood alone: accept iff loglik(x') - loglik(x) > log u.
+   The reference compares the whole update weight, which counts the prior of
+   the moved address twice and leaves prior^2 x likelihood invariant; that
+   arithmetic is deliberately not reproduced.  No step size, no rejection; a
+   move is capped at 64 shrinks, after which the particle stays where it is
+   and counts in *exhausted.  selection: one address (the regression: :slope
+   or :intercept, not both: GH_E_INVAL).  Families, calling rules and refusals
+   as gh_pf_choice_gradients; draw windows and the per-step move counter are
+   shared with gh_pf_rejuvenate.  Log weights are unchanged.  *shrinks (total
+   over particles and moves) and *exhausted are optional and synchronise. */
+int gh_pf_elliptical_slice(gh_pf* pf, uint32_t selection, int n_moves, int64_t* shrinks /* nullable */,
+                           int64_t* exhausted /* nullable */);
+/* map_optimize(trace, selection; max_step_size, tau, min_step_size) on every
+   particle, n_iters times (src/inference/map_optimize.jl:9-41): backtracking
+   gradient ascent on the step's score over the selected components of the
+   current latent — try x + step grad(x) from step = max_step_size, multiply
+   step by tau while the score got worse, give up (keep x) once step <
+   min_step_size.  max_step_size and min_step_size finite and > 0, tau in
+   (0, 1), and at most 1100 backtracking steps from max to min (GH_E_INVAL
+   otherwise).  Draws nothing: the per-step move counter does not advance.
+   Families, calling rules and refusals as gh_pf_choice_gradients.  Log
+   weights are unchanged.  *improved (optional, synchronises): iterations that
+   moved, over this rank's particles. */
+int gh_pf_map_optimize(gh_pf* pf, uint32_t selection, double max_step_size, double tau, double min_step_size,
+                       int n_iters, int64_t* improved /* nullable */);
 /* Conditional SMC (examples/pmmh/smc.jl:100-151, the particle-Gibbs sweep):
    particle 0 is the distinguished particle, pinned to ref_x1 at init and to
    ref_xt at each step, its parent always itself, its weight the observation
