@@ -3698,175 +3698,69 @@ extern "C" int gh_pf_get_parents(gh_pf* pf, int64_t* out) {
   return GH_OK;
 }
 
-// ------------------------------------------------------------ rejuvenation
-template <class Model>
-static void launch_rejuv_t(gh_pf* pf, const typename Model::Params& p, const RejuvArgs& a, bool init) {
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  if (init)
-    hipLaunchKernelGGL((k_rejuv<Model, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                       pf->last_obs, a);
-  else
-    hipLaunchKernelGGL((k_rejuv<Model, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                       pf->last_obs, a);
-}
+// ------------------------------------------------ moves on the particles
+// mh (selection and drift forms), choice_gradients, mala, hmc,
+// elliptical_slice and map_optimize on every particle (gh_rejuv.h, gh_grad.h,
+// gh_slice.h).  The states of step t are rewritten in place; the parent
+// states are those step t consumed: the previous slot through the step's
+// ancestors, or rows received from other ranks (still resident until the next
+// exchange).  Every entry point: its own argument checks, move_begin (the
+// refusals, all before any launch), move_run.
 
-static int launch_rejuv(gh_pf* pf, const RejuvArgs& a, bool init) {
-  CHECK(with_model(pf->m, [&](auto model, const auto& p) { launch_rejuv_t<decltype(model)>(pf, p, a, init); }));
-  HIP_TRY(hipGetLastError());
-  return GH_OK;
-}
-
-// mh(trace, select(x_t)) on every particle (gh_rejuv.h).  The states of step t
-// are rewritten in place; the parent states are those step t consumed: the
-// previous slot through the step's ancestors, or rows received from other
-// ranks (still resident until the next exchange).
 // latent addresses of the current step a selection may name (bit i = address i)
 static uint32_t latent_addresses(const gh_model* m) { return m->family == GH_FAMILY_REGRESSION ? 3u : 1u; }
 
-extern "C" int gh_pf_rejuvenate(gh_pf* pf, int n_moves, int64_t* accepted) {
-  if (!pf) return set_err(GH_E_INVAL, "null pf");
-  return gh_pf_mh_select(pf, latent_addresses(pf->m), n_moves, accepted);
+// What a move admits: the families its kernel is written for, and (kAdmitGrad)
+// no filter sharded over ranks.
+enum MoveAdmits {
+  kAdmitAny,         // mh's selection form: every family
+  kAdmitContinuous,  // the drift: a continuous latent
+  kAdmitGrad,        // Grad<Model>: the LG-SSM, the nonlinear SSM, the regression; one rank
+};
+
+// the families Grad<Model> is written for
+template <class M>
+struct has_grad : std::false_type {};
+template <int D, int S>
+struct has_grad<LGModel<D, S>> : std::true_type {};
+template <>
+struct has_grad<KitModel> : std::true_type {};
+template <>
+struct has_grad<RegModel> : std::true_type {};
+
+// the model types a move's kernel is instantiated for (move_begin refuses the
+// rest at run time; a slot model's latent kind is known only there)
+template <MoveAdmits A, class M>
+constexpr bool move_admits() {
+  return A == kAdmitAny || (A == kAdmitContinuous && !std::is_same<M, HMMModel>::value) ||
+         (A == kAdmitGrad && has_grad<M>::value);
 }
 
-extern "C" int gh_pf_mh_select(gh_pf* pf, uint32_t selection, int n_moves, int64_t* accepted) {
-  if (!pf) return set_err(GH_E_INVAL, "null pf");
-  if (n_moves < 0) return set_err(GH_E_INVAL, "gh_pf_rejuvenate: n_moves < 0");
-  if (selection == 0 || (selection & ~latent_addresses(pf->m)) != 0)
-    return set_err(GH_E_INVAL, "gh_pf_mh_select: selection 0x%x names no latent address of this step (valid: 0x%x)",
-                   selection, latent_addresses(pf->m));
-  if (pf->m->family == GH_FAMILY_REGRESSION && pf->t != 1)
-    return set_err(GH_E_STATE, "gh_pf_mh_select: the regression is a static model (t = 1)");
-  if (pf->resample_calls > 0)
-    return set_err(GH_E_STATE, "gh_pf_rejuvenate: call after a step and before maybe_resample");
-  if (pf->cond) return set_err(GH_E_STATE, "gh_pf_rejuvenate: the distinguished particle of a conditional filter is fixed");
-  if ((uint64_t)pf->rejuv_moves + (uint64_t)n_moves > kRejuvMaxMoves)
-    return set_err(GH_E_INVAL, "gh_pf_rejuvenate: more than %u moves at one step", kRejuvMaxMoves);
-  HIP_TRY(hipSetDevice(pf->ctx->device));
-  if (!pf->acc_count) HIP_TRY(hipMalloc(&pf->acc_count, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(pf->acc_count, 0, sizeof(unsigned long long), pf->s));
-  const int t = pf->t;
-  if (n_moves > 0 && pf->n > 0) {
-    RejuvArgs a{};
-    if (t >= 2) {
-      a.xprev = slot_x(pf, t - 1);
-      a.anc = anc_for_step(pf, t);
-      a.res = pf->res_hist + t;
-      a.remote = pf->rows_recv;
-      a.ld_remote = pf->D + 1;
-    }
-    a.x = slot_x(pf, t);
-    a.n = pf->n;
-    a.lo = pf->lo;
-    a.seed = pf->seed;
-    a.t = (uint32_t)t;
-    a.move0 = pf->rejuv_moves;
-    a.select = selection;
-    a.n_moves = n_moves;
-    a.accepted = pf->acc_count;
-    CHECK(launch_rejuv(pf, a, t == 1));
-  }
-  pf->rejuv_moves += (uint32_t)n_moves;
-  if (accepted) {
-    unsigned long long h = 0;
-    CHECK(d2h(pf, &h, pf->acc_count, sizeof h));
-    *accepted = (int64_t)h;
-  }
-  return GH_OK;
-}
-
-// mh(trace, drift, (sd,)) on every particle (gh_rejuv.h k_mh_drift)
-extern "C" int gh_pf_mh_drift(gh_pf* pf, uint32_t selection, const double* sd, int n_moves, int64_t* accepted) {
-  if (!pf || !sd) return set_err(GH_E_INVAL, "gh_pf_mh_drift: null argument");
-  if (n_moves < 0) return set_err(GH_E_INVAL, "gh_pf_mh_drift: n_moves < 0");
-  if (pf->m->family == GH_FAMILY_HMM ||
-      (pf->m->family == GH_FAMILY_SLOTS &&
-       (pf->m->slots.lat == SLOT_LAT_CATEGORICAL || pf->m->slots.lat == SLOT_LAT_SWITCHING)))
-    return set_err(GH_E_INVAL, "gh_pf_mh_drift: a Gaussian drift needs a continuous latent (not a categorical one)");
-  if (selection == 0 || (selection & ~latent_addresses(pf->m)) != 0)
-    return set_err(GH_E_INVAL, "gh_pf_mh_drift: selection 0x%x names no latent address of this step (valid: 0x%x)",
-                   selection, latent_addresses(pf->m));
-  if (pf->m->family == GH_FAMILY_REGRESSION && pf->t != 1)
-    return set_err(GH_E_STATE, "gh_pf_mh_drift: the regression is a static model (t = 1)");
-  if (pf->resample_calls > 0) return set_err(GH_E_STATE, "gh_pf_mh_drift: call after a step and before maybe_resample");
-  if (pf->cond) return set_err(GH_E_STATE, "gh_pf_mh_drift: the distinguished particle of a conditional filter is fixed");
-  if ((uint64_t)pf->rejuv_moves + (uint64_t)n_moves > kRejuvMaxMoves)
-    return set_err(GH_E_INVAL, "gh_pf_mh_drift: more than %u moves at one step", kRejuvMaxMoves);
-  const int D = pf->D;
-  DriftSd dsd{};
-  for (int k = 0; k < D; ++k) {
-    // the regression's components are its addresses; an Unfold latent drifts as a whole
-    const bool sel = pf->m->family == GH_FAMILY_REGRESSION ? ((selection >> k) & 1u) != 0 : true;
-    if (sel && !(sd[k] > 0.0 && sd[k] < INFINITY))
-      return set_err(GH_E_INVAL, "gh_pf_mh_drift: sd[%d] = %g must be finite and > 0", k, sd[k]);
-    dsd.v[k] = sel ? sd[k] : 0.0;
-  }
-  HIP_TRY(hipSetDevice(pf->ctx->device));
-  if (!pf->acc_count) HIP_TRY(hipMalloc(&pf->acc_count, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(pf->acc_count, 0, sizeof(unsigned long long), pf->s));
-  const int t = pf->t;
-  if (n_moves > 0 && pf->n > 0) {
-    RejuvArgs a{};
-    if (t >= 2) {
-      a.xprev = slot_x(pf, t - 1);
-      a.anc = anc_for_step(pf, t);
-      a.res = pf->res_hist + t;
-      a.remote = pf->rows_recv;
-      a.ld_remote = pf->D + 1;
-    }
-    a.x = slot_x(pf, t);
-    a.n = pf->n;
-    a.lo = pf->lo;
-    a.seed = pf->seed;
-    a.t = (uint32_t)t;
-    a.move0 = pf->rejuv_moves;
-    a.select = selection;
-    a.n_moves = n_moves;
-    a.accepted = pf->acc_count;
-    const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-    CHECK(with_model(pf->m, [&](auto model, const auto& p) {
-      using M = decltype(model);
-      if constexpr (!std::is_same<M, HMMModel>::value) {
-        if (t == 1)
-          hipLaunchKernelGGL((k_mh_drift<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                             pf->last_obs, a, dsd);
-        else
-          hipLaunchKernelGGL((k_mh_drift<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                             pf->last_obs, a, dsd);
-      }
-    }));
-    HIP_TRY(hipGetLastError());
-  }
-  pf->rejuv_moves += (uint32_t)n_moves;
-  if (accepted) {
-    unsigned long long h = 0;
-    CHECK(d2h(pf, &h, pf->acc_count, sizeof h));
-    *accepted = (int64_t)h;
-  }
-  return GH_OK;
-}
-
-// ------------------------------------------------------- gradient moves
-// (gh_grad.h: choice_gradients, mala, hmc).  The refusals shared by the three
-// entry points, all before any launch.
-static int grad_check(const gh_pf* pf, const char* fn, uint32_t selection, int n_moves) {
+// The refusals shared by the moves, in one order for all of them.
+static int move_begin(const gh_pf* pf, const char* fn, uint32_t selection, int n_moves, MoveAdmits admits) {
+  const gh_model* m = pf->m;
   if (n_moves < 0) return set_err(GH_E_INVAL, "%s: n_moves < 0", fn);
-  if (pf->m->family == GH_FAMILY_HMM || pf->m->family == GH_FAMILY_SLOTS)
+  if (admits == kAdmitContinuous &&
+      (m->family == GH_FAMILY_HMM ||
+       (m->family == GH_FAMILY_SLOTS && (m->slots.lat == SLOT_LAT_CATEGORICAL || m->slots.lat == SLOT_LAT_SWITCHING))))
+    return set_err(GH_E_INVAL, "%s: a Gaussian drift needs a continuous latent (not a categorical one)", fn);
+  if (admits == kAdmitGrad && (m->family == GH_FAMILY_HMM || m->family == GH_FAMILY_SLOTS))
     return set_err(GH_E_INVAL, "%s: not lowered for this model (the gradients are closed forms of the LG-SSM, the "
                                "nonlinear SSM and the regression)", fn);
-  if (selection == 0 || (selection & ~latent_addresses(pf->m)) != 0)
+  if (selection == 0 || (selection & ~latent_addresses(m)) != 0)
     return set_err(GH_E_INVAL, "%s: selection 0x%x names no latent address of this step (valid: 0x%x)", fn, selection,
-                   latent_addresses(pf->m));
-  if (pf->m->family == GH_FAMILY_REGRESSION && pf->t != 1)
+                   latent_addresses(m));
+  if (m->family == GH_FAMILY_REGRESSION && pf->t != 1)
     return set_err(GH_E_STATE, "%s: the regression is a static model (t = 1)", fn);
   if (pf->resample_calls > 0) return set_err(GH_E_STATE, "%s: call after a step and before maybe_resample", fn);
   if (pf->cond) return set_err(GH_E_STATE, "%s: the distinguished particle of a conditional filter is fixed", fn);
-  if (mr(pf->ctx)) return set_err(GH_E_STATE, "%s: not for a filter sharded over ranks", fn);
+  if (admits == kAdmitGrad && mr(pf->ctx)) return set_err(GH_E_STATE, "%s: not for a filter sharded over ranks", fn);
   if ((uint64_t)pf->rejuv_moves + (uint64_t)n_moves > kRejuvMaxMoves)
     return set_err(GH_E_INVAL, "%s: more than %u moves at one step", fn, kRejuvMaxMoves);
   return GH_OK;
 }
 
-static RejuvArgs grad_args(gh_pf* pf, uint32_t selection, int n_moves) {
+static RejuvArgs move_args(gh_pf* pf, uint32_t selection, int n_moves) {
   RejuvArgs a{};
   const int t = pf->t;
   if (t >= 2) {
@@ -3888,19 +3782,87 @@ static RejuvArgs grad_args(gh_pf* pf, uint32_t selection, int n_moves) {
   return a;
 }
 
-// the families Grad<Model> is written for (grad_check refuses the others)
-template <class M>
-struct has_grad : std::false_type {};
-template <int D, int S>
-struct has_grad<LGModel<D, S>> : std::true_type {};
-template <>
-struct has_grad<KitModel> : std::true_type {};
-template <>
-struct has_grad<RegModel> : std::true_type {};
+// a one-word device counter: allocated at its first use, zeroed on the filter's stream
+static int counter_clear(gh_pf* pf, unsigned long long** c) {
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  if (!*c) HIP_TRY(hipMalloc(c, sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(*c, 0, sizeof(unsigned long long), pf->s));
+  return GH_OK;
+}
+
+static int counter_read(gh_pf* pf, const unsigned long long* c, int64_t* out) {
+  if (!out) return GH_OK;
+  unsigned long long h = 0;
+  CHECK(d2h(pf, &h, c, sizeof h));
+  *out = (int64_t)h;
+  return GH_OK;
+}
+
+// kernel K<M, INIT> (INIT: t == 1) over the filter's particles; the trailing
+// arguments follow RejuvArgs
+#define MOVE_LAUNCH(K, M, pf, p, a, ...)                                                                          \
+  do {                                                                                                            \
+    const dim3 grid_((unsigned)(pf)->nb_step), block_(kBlock);                                                    \
+    if ((pf)->t == 1)                                                                                             \
+      hipLaunchKernelGGL((K<M, true>), grid_, block_, 0, (pf)->s, (const double*)(pf)->m->dparams, p,             \
+                         (pf)->last_obs, a, ##__VA_ARGS__);                                                       \
+    else                                                                                                          \
+      hipLaunchKernelGGL((K<M, false>), grid_, block_, 0, (pf)->s, (const double*)(pf)->m->dparams, p,            \
+                         (pf)->last_obs, a, ##__VA_ARGS__);                                                       \
+  } while (0)
+
+// After move_begin: launch(model, p, a) starts the kernel of the filter's model
+// type; *count receives the kernel's counter.  draws: the moves consume draw
+// windows (the step's move counter advances); map_optimize draws nothing.
+template <MoveAdmits A, class K>
+static int move_run(gh_pf* pf, uint32_t selection, int n_moves, int64_t* count, K&& launch, bool draws = true) {
+  CHECK(counter_clear(pf, &pf->acc_count));
+  if (n_moves > 0 && pf->n > 0) {
+    const RejuvArgs a = move_args(pf, selection, n_moves);
+    CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+      if constexpr (move_admits<A, decltype(model)>()) launch(model, p, a);
+    }));
+    HIP_TRY(hipGetLastError());
+  }
+  if (draws) pf->rejuv_moves += (uint32_t)n_moves;
+  return counter_read(pf, pf->acc_count, count);
+}
+
+extern "C" int gh_pf_rejuvenate(gh_pf* pf, int n_moves, int64_t* accepted) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  return gh_pf_mh_select(pf, latent_addresses(pf->m), n_moves, accepted);
+}
+
+// mh(trace, select(x_t)) on every particle (gh_rejuv.h k_rejuv)
+extern "C" int gh_pf_mh_select(gh_pf* pf, uint32_t selection, int n_moves, int64_t* accepted) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  CHECK(move_begin(pf, "gh_pf_mh_select", selection, n_moves, kAdmitAny));
+  return move_run<kAdmitAny>(pf, selection, n_moves, accepted, [&](auto model, const auto& p, const RejuvArgs& a) {
+    MOVE_LAUNCH(k_rejuv, decltype(model), pf, p, a);
+  });
+}
+
+// mh(trace, drift, (sd,)) on every particle (gh_rejuv.h k_mh_drift)
+extern "C" int gh_pf_mh_drift(gh_pf* pf, uint32_t selection, const double* sd, int n_moves, int64_t* accepted) {
+  if (!pf || !sd) return set_err(GH_E_INVAL, "gh_pf_mh_drift: null argument");
+  CHECK(move_begin(pf, "gh_pf_mh_drift", selection, n_moves, kAdmitContinuous));
+  DriftSd dsd{};
+  for (int k = 0; k < pf->D; ++k) {
+    // the regression's components are its addresses; an Unfold latent drifts as a whole
+    const bool sel = pf->m->family == GH_FAMILY_REGRESSION ? ((selection >> k) & 1u) != 0 : true;
+    if (sel && !(sd[k] > 0.0 && sd[k] < INFINITY))
+      return set_err(GH_E_INVAL, "gh_pf_mh_drift: sd[%d] = %g must be finite and > 0", k, sd[k]);
+    dsd.v[k] = sel ? sd[k] : 0.0;
+  }
+  return move_run<kAdmitContinuous>(pf, selection, n_moves, accepted,
+                                    [&](auto model, const auto& p, const RejuvArgs& a) {
+                                      MOVE_LAUNCH(k_mh_drift, decltype(model), pf, p, a, dsd);
+                                    });
+}
 
 extern "C" int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* host_values, double* host_grads) {
   if (!pf || !host_grads) return set_err(GH_E_INVAL, "gh_pf_choice_gradients: null argument");
-  CHECK(grad_check(pf, "gh_pf_choice_gradients", selection, 0));
+  CHECK(move_begin(pf, "gh_pf_choice_gradients", selection, 0, kAdmitGrad));
   HIP_TRY(hipSetDevice(pf->ctx->device));
   if (host_values) CHECK(gh_pf_get_states(pf, host_values));
   const int64_t n = pf->n;
@@ -3909,19 +3871,10 @@ extern "C" int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* hos
   DBuf d;
   const size_t doubles = (size_t)slot_doubles(n, D);
   CHECK(dalloc(d, sizeof(double) * doubles));
-  const RejuvArgs a = grad_args(pf, selection, 0);
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  const bool init = pf->t == 1;
+  const RejuvArgs a = move_args(pf, selection, 0);
   CHECK(with_model(pf->m, [&](auto model, const auto& p) {
     using M = decltype(model);
-    if constexpr (has_grad<M>::value) {
-      if (init)
-        hipLaunchKernelGGL((k_choice_gradients<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                           pf->last_obs, a, d.as<double>());
-      else
-        hipLaunchKernelGGL((k_choice_gradients<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                           pf->last_obs, a, d.as<double>());
-    }
+    if constexpr (move_admits<kAdmitGrad, M>()) MOVE_LAUNCH(k_choice_gradients, M, pf, p, a, d.as<double>());
   }));
   HIP_TRY(hipGetLastError());
   std::vector<double> tiled(doubles);
@@ -3931,94 +3884,38 @@ extern "C" int gh_pf_choice_gradients(gh_pf* pf, uint32_t selection, double* hos
   return GH_OK;
 }
 
-// mala / hmc / elliptical_slice / map_optimize: K launches the kernel of one
-// model type (init: t == 1).  draws: the moves consume draw windows (the
-// step's move counter advances); map_optimize draws nothing.
-template <class K>
-static int grad_move(gh_pf* pf, const char* fn, uint32_t selection, int n_moves, int64_t* accepted, K&& launch,
-                     bool draws = true) {
-  CHECK(grad_check(pf, fn, selection, draws ? n_moves : 0));
-  HIP_TRY(hipSetDevice(pf->ctx->device));
-  if (!pf->acc_count) HIP_TRY(hipMalloc(&pf->acc_count, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(pf->acc_count, 0, sizeof(unsigned long long), pf->s));
-  if (n_moves > 0 && pf->n > 0) {
-    const RejuvArgs a = grad_args(pf, selection, n_moves);
-    CHECK(with_model(pf->m, [&](auto model, const auto& p) {
-      if constexpr (has_grad<decltype(model)>::value) launch(model, p, a, pf->t == 1);
-    }));
-    HIP_TRY(hipGetLastError());
-  }
-  if (draws) pf->rejuv_moves += (uint32_t)n_moves;
-  if (accepted) {
-    unsigned long long h = 0;
-    CHECK(d2h(pf, &h, pf->acc_count, sizeof h));
-    *accepted = (int64_t)h;
-  }
-  return GH_OK;
-}
-
 extern "C" int gh_pf_mala(gh_pf* pf, uint32_t selection, double tau, int n_moves, int64_t* accepted) {
   if (!pf) return set_err(GH_E_INVAL, "gh_pf_mala: null pf");
   if (!(tau > 0.0 && tau < INFINITY)) return set_err(GH_E_INVAL, "gh_pf_mala: tau = %g must be finite and > 0", tau);
+  CHECK(move_begin(pf, "gh_pf_mala", selection, n_moves, kAdmitGrad));
   const double sd = sqrt(2.0 * tau);
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  return grad_move(pf, "gh_pf_mala", selection, n_moves, accepted,
-                   [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
-                     using M = decltype(model);
-                     if (init)
-                       hipLaunchKernelGGL((k_mala<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                                          pf->last_obs, a, tau, sd);
-                     else
-                       hipLaunchKernelGGL((k_mala<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                                          pf->last_obs, a, tau, sd);
-                   });
+  return move_run<kAdmitGrad>(pf, selection, n_moves, accepted, [&](auto model, const auto& p, const RejuvArgs& a) {
+    MOVE_LAUNCH(k_mala, decltype(model), pf, p, a, tau, sd);
+  });
 }
 
 extern "C" int gh_pf_hmc(gh_pf* pf, uint32_t selection, int L, double eps, int n_moves, int64_t* accepted) {
   if (!pf) return set_err(GH_E_INVAL, "gh_pf_hmc: null pf");
   if (L < 1) return set_err(GH_E_INVAL, "gh_pf_hmc: L = %d leapfrog steps (at least 1)", L);
   if (!(eps > 0.0 && eps < INFINITY)) return set_err(GH_E_INVAL, "gh_pf_hmc: eps = %g must be finite and > 0", eps);
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  return grad_move(pf, "gh_pf_hmc", selection, n_moves, accepted,
-                   [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
-                     using M = decltype(model);
-                     if (init)
-                       hipLaunchKernelGGL((k_hmc<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                                          pf->last_obs, a, L, eps);
-                     else
-                       hipLaunchKernelGGL((k_hmc<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                                          pf->last_obs, a, L, eps);
-                   });
+  CHECK(move_begin(pf, "gh_pf_hmc", selection, n_moves, kAdmitGrad));
+  return move_run<kAdmitGrad>(pf, selection, n_moves, accepted, [&](auto model, const auto& p, const RejuvArgs& a) {
+    MOVE_LAUNCH(k_hmc, decltype(model), pf, p, a, L, eps);
+  });
 }
 
-// ------------------------------------ elliptical slice, map_optimize
-// (gh_slice.h).  The refusals are grad_check's, all before any launch.
 extern "C" int gh_pf_elliptical_slice(gh_pf* pf, uint32_t selection, int n_moves, int64_t* shrinks,
                                       int64_t* exhausted) {
   static const char* fn = "gh_pf_elliptical_slice";
   if (!pf) return set_err(GH_E_INVAL, "gh_pf_elliptical_slice: null pf");
-  CHECK(grad_check(pf, fn, selection, n_moves));
+  CHECK(move_begin(pf, fn, selection, n_moves, kAdmitGrad));
   if (pf->m->family == GH_FAMILY_REGRESSION && selection == latent_addresses(pf->m))
     return set_err(GH_E_INVAL, "%s: selection 0x%x names both addresses; the slice moves one address", fn, selection);
-  HIP_TRY(hipSetDevice(pf->ctx->device));
-  if (!pf->exh_count) HIP_TRY(hipMalloc(&pf->exh_count, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(pf->exh_count, 0, sizeof(unsigned long long), pf->s));
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  CHECK(grad_move(pf, fn, selection, n_moves, shrinks, [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
-    using M = decltype(model);
-    if (init)
-      hipLaunchKernelGGL((k_elliptical_slice<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                         pf->last_obs, a, pf->exh_count);
-    else
-      hipLaunchKernelGGL((k_elliptical_slice<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                         pf->last_obs, a, pf->exh_count);
+  CHECK(counter_clear(pf, &pf->exh_count));
+  CHECK(move_run<kAdmitGrad>(pf, selection, n_moves, shrinks, [&](auto model, const auto& p, const RejuvArgs& a) {
+    MOVE_LAUNCH(k_elliptical_slice, decltype(model), pf, p, a, pf->exh_count);
   }));
-  if (exhausted) {
-    unsigned long long h = 0;
-    CHECK(d2h(pf, &h, pf->exh_count, sizeof h));
-    *exhausted = (int64_t)h;
-  }
-  return GH_OK;
+  return counter_read(pf, pf->exh_count, exhausted);
 }
 
 extern "C" int gh_pf_map_optimize(gh_pf* pf, uint32_t selection, double max_step_size, double tau,
@@ -4036,17 +3933,11 @@ extern "C" int gh_pf_map_optimize(gh_pf* pf, uint32_t selection, double max_step
   if (!(halvings <= (double)kMapMaxBacktracks))
     return set_err(GH_E_INVAL, "%s: %g backtracking steps from %g down to %g by tau = %g (at most %d)", fn, halvings,
                    max_step_size, min_step_size, tau, kMapMaxBacktracks);
-  const dim3 grid((unsigned)pf->nb_step), block(kBlock);
-  return grad_move(
-      pf, fn, selection, n_iters, improved,
-      [&](auto model, const auto& p, const RejuvArgs& a, bool init) {
-        using M = decltype(model);
-        if (init)
-          hipLaunchKernelGGL((k_map_optimize<M, true>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                             pf->last_obs, a, max_step_size, tau, min_step_size);
-        else
-          hipLaunchKernelGGL((k_map_optimize<M, false>), grid, block, 0, pf->s, (const double*)pf->m->dparams, p,
-                             pf->last_obs, a, max_step_size, tau, min_step_size);
+  CHECK(move_begin(pf, fn, selection, 0, kAdmitGrad));  // (draws nothing: no window to run out of)
+  return move_run<kAdmitGrad>(
+      pf, selection, n_iters, improved,
+      [&](auto model, const auto& p, const RejuvArgs& a) {
+        MOVE_LAUNCH(k_map_optimize, decltype(model), pf, p, a, max_step_size, tau, min_step_size);
       },
       false);
 }

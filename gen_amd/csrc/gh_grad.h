@@ -191,31 +191,13 @@ struct GradWaves<LGModel<D, S>> {
   static constexpr int kGrad = D <= 4 ? 8 : (D <= 10 ? 4 : 2);
 };
 
-// bit k of the selection for the regression's two addresses; an Unfold latent
-// moves as a whole (gh_pf_mh_drift's rule)
-template <class Model>
-__device__ __forceinline__ bool grad_selected(uint32_t select, int k) {
-  if constexpr (std::is_same<Model, RegModel>::value) return ((select >> k) & 1u) != 0;
-  return true;
-}
-
-// the parent's state of particle j (k_mh_drift's read)
-template <int D, bool INIT>
-__device__ __forceinline__ void grad_load(const RejuvArgs& a, int64_t j, double* x, double* xp) {
-#pragma unroll
-  for (int k = 0; k < D; ++k) x[k] = a.x[xidx(j, k, D)];
-#pragma unroll
-  for (int k = 0; k < D; ++k) xp[k] = 0.0;
-  if (!INIT) {
-    const int64_t src = *a.res ? (int64_t)a.anc[j] : j;
-    if (src >= 0) {
-#pragma unroll
-      for (int k = 0; k < D; ++k) xp[k] = a.xprev[xidx(src, k, D)];
-    } else {
-#pragma unroll
-      for (int k = 0; k < D; ++k) xp[k] = ld_sys(&a.remote[(-1 - src) * a.ld_remote + k]);
-    }
-  }
+// particle j's state x and what Grad keeps of its parent's
+template <class Model, bool INIT>
+__device__ __forceinline__ void grad_prep(const typename Model::Params& p, const StepObs& o, const RejuvArgs& a,
+                                          int64_t j, double* x, typename Grad<Model>::Ctx& c) {
+  double xp[Model::kD];
+  move_load<Model::kD, INIT>(a, j, x, xp);
+  Grad<Model>::prep(p, o, a.t, xp, c);
 }
 
 // choice_gradients(trace, selection) on every particle: the gradient of the
@@ -229,13 +211,12 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kGrad) void k_choice_grad
   const typename Model::Params p = p0.rebase(prm);
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (j >= a.n) return;
-  double x[D], xp[D], g[D];
-  grad_load<D, INIT>(a, j, x, xp);
+  double x[D], g[D];
   typename G::Ctx c;
-  G::prep(p, o, a.t, xp, c);
+  grad_prep<Model, INIT>(p, o, a, j, x, c);
   G::eval(p, o, a.t, c, x, g);
 #pragma unroll
-  for (int k = 0; k < D; ++k) out[xidx(j, k, D)] = grad_selected<Model>(a.select, k) ? g[k] : 0.0;
+  for (int k = 0; k < D; ++k) out[xidx(j, k, D)] = move_selected<Model>(a.select, k) ? g[k] : 0.0;
 }
 
 // mala(trace, selection, tau) on every particle (src/inference/mala.jl:11-54):
@@ -244,8 +225,8 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kGrad) void k_choice_grad
 //   log(rand()) < (s(y) - s(x)) - sum logN(y_k; muf_k, std) + sum logN(x_k; mub_k, std),
 // mub = y + tau g(y).  The normal densities' constants cancel: the two sums are
 // (qf - qb) / (4 tau), qf = sum (y_k - muf_k)^2, qb = sum (x_k - mub_k)^2, each
-// accumulated by fma over k ascending.  Draws: move w's window as k_mh_drift
-// (z[k] for component k from its first blocks, the uniform from its last).
+// accumulated by fma over k ascending.  Draws: move w's window (z[k] for
+// component k from its first blocks, the uniform from its last; move_accept).
 // s and g of the accepted point are carried into the next move.
 template <class Model, bool INIT>
 __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const double* __restrict__ prm,
@@ -254,9 +235,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const 
   constexpr int D = Model::kD;
   using G = Grad<Model>;
   const typename Model::Params p = p0.rebase(prm);
-  __shared__ double tab[kMathTabDoubles];
-  load_math_tab(tab);
-  lds_barrier();
+  const double* tab = move_tab();
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   unsigned acc = 0;
   if (j < a.n) {
@@ -264,11 +243,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const 
     const double inv4tau = 1.0 / (4.0 * tau);
     double x[D], g[D], y[D], gy[D];
     typename G::Ctx c;
-    {
-      double xp[D];
-      grad_load<D, INIT>(a, j, x, xp);
-      G::prep(p, o, a.t, xp, c);
-    }
+    grad_prep<Model, INIT>(p, o, a, j, x, c);
     double s = G::eval(p, o, a.t, c, x, g);
     for (int m = 0; m < a.n_moves; ++m) {
       const Draw dr = rejuv_draw(a.move0 + (uint32_t)m);
@@ -278,7 +253,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const 
         normals_n<D>(a.seed, pid, a.t, dr.stream, dr.base, z, tab);
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-          if (grad_selected<Model>(a.select, k)) {
+          if (move_selected<Model>(a.select, k)) {
             const double muf = fma(tau, g[k], x[k]);
             y[k] = fma(sd, z[k], muf);
             const double e = y[k] - muf;
@@ -292,15 +267,12 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const 
       double qb = 0.0;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        if (grad_selected<Model>(a.select, k)) {
+        if (move_selected<Model>(a.select, k)) {
           const double e = x[k] - fma(tau, gy[k], y[k]);
           qb = fma(e, e, qb);
         }
       }
-      const double alpha = (s2 - s) + (qf - qb) * inv4tau;
-      const u32x4 w = rng_block(a.seed, pid, a.t, dr.stream, dr.base + kRejuvDraws - 1);
-      const double logu = gh_log(u53(w.x, w.y));
-      if (logu < alpha) {
+      if (move_accept(a, pid, dr, (s2 - s) + (qf - qb) * inv4tau)) {
 #pragma unroll
         for (int k = 0; k < D; ++k) {
           x[k] = y[k];
@@ -313,8 +285,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kMala) void k_mala(const 
 #pragma unroll
     for (int k = 0; k < D; ++k) a.x[xidx(j, k, D)] = x[k];
   }
-  const uint64_t tot = wave_sum_u64((uint64_t)acc);
-  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(a.accepted, (unsigned long long)tot);
+  move_count(a.accepted, acc);
 }
 
 // hmc(trace, selection; L, eps) on every particle (src/inference/hmc.jl:25-72):
@@ -330,9 +301,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
   constexpr int D = Model::kD;
   using G = Grad<Model>;
   const typename Model::Params p = p0.rebase(prm);
-  __shared__ double tab[kMathTabDoubles];
-  load_math_tab(tab);
-  lds_barrier();
+  const double* tab = move_tab();
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   unsigned acc = 0;
   if (j < a.n) {
@@ -340,11 +309,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
     const double heps = 0.5 * eps;
     double x[D], g[D], q[D], gq[D], mom[D];
     typename G::Ctx c;
-    {
-      double xp[D];
-      grad_load<D, INIT>(a, j, x, xp);
-      G::prep(p, o, a.t, xp, c);
-    }
+    grad_prep<Model, INIT>(p, o, a, j, x, c);
     double s = G::eval(p, o, a.t, c, x, g);
     for (int m = 0; m < a.n_moves; ++m) {
       const Draw dr = rejuv_draw(a.move0 + (uint32_t)m);
@@ -354,7 +319,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
         normals_n<D>(a.seed, pid, a.t, dr.stream, dr.base, z, tab);
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-          const bool sel = grad_selected<Model>(a.select, k);
+          const bool sel = move_selected<Model>(a.select, k);
           mom[k] = sel ? z[k] : 0.0;
           if (sel) k0 = fma(z[k], z[k], k0);
           q[k] = x[k];
@@ -365,7 +330,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
       for (int l = 0; l < L; ++l) {
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-          if (grad_selected<Model>(a.select, k)) {
+          if (move_selected<Model>(a.select, k)) {
             mom[k] = fma(heps, gq[k], mom[k]);
             q[k] = fma(eps, mom[k], q[k]);
           }
@@ -373,18 +338,15 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
         sq = G::eval(p, o, a.t, c, q, gq);
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-          if (grad_selected<Model>(a.select, k)) mom[k] = fma(heps, gq[k], mom[k]);
+          if (move_selected<Model>(a.select, k)) mom[k] = fma(heps, gq[k], mom[k]);
         }
       }
       double k1 = 0.0;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        if (grad_selected<Model>(a.select, k)) k1 = fma(mom[k], mom[k], k1);
+        if (move_selected<Model>(a.select, k)) k1 = fma(mom[k], mom[k], k1);
       }
-      const double alpha = (sq - s) + (-0.5 * k1 - -0.5 * k0);
-      const u32x4 w = rng_block(a.seed, pid, a.t, dr.stream, dr.base + kRejuvDraws - 1);
-      const double logu = gh_log(u53(w.x, w.y));
-      if (logu < alpha) {
+      if (move_accept(a, pid, dr, (sq - s) + (-0.5 * k1 - -0.5 * k0))) {
 #pragma unroll
         for (int k = 0; k < D; ++k) {
           x[k] = q[k];
@@ -397,8 +359,7 @@ __global__ __launch_bounds__(kBlock, GradWaves<Model>::kHmc) void k_hmc(const do
 #pragma unroll
     for (int k = 0; k < D; ++k) a.x[xidx(j, k, D)] = x[k];
   }
-  const uint64_t tot = wave_sum_u64((uint64_t)acc);
-  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(a.accepted, (unsigned long long)tot);
+  move_count(a.accepted, acc);
 }
 
 }  // namespace gh

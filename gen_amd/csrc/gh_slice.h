@@ -146,9 +146,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kSlice) void k_elliptica
   using G = Grad<Model>;
   using P = SlicePrior<Model>;
   const typename Model::Params p = p0.rebase(prm);
-  __shared__ double tab[kMathTabDoubles];
-  load_math_tab(tab);
-  lds_barrier();
+  const double* tab = move_tab();
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   unsigned shr = 0, exh = 0;
   if (j < a.n) {
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kSlice) void k_elliptica
     {
       double xp[D];
       typename G::Ctx c;
-      grad_load<D, INIT>(a, j, x, xp);
+      move_load<D, INIT>(a, j, x, xp);
       G::prep(p, o, a.t, xp, c);
       P::mean(p, c, mu);
     }
@@ -174,8 +172,8 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kSlice) void k_elliptica
       }
 #pragma unroll
       for (int k = 0; k < D; ++k) f[k] = x[k] - mu[k];
-      const u32x4 b = rng_block(a.seed, pid, a.t, dr.stream, dr.base + kRejuvDraws - 1);
-      const double logu = gh_log(u53(b.x, b.y));
+      const u32x4 b = move_uniform_block(a, pid, dr);
+      const double logu = move_logu(b);
       double theta = kTwoPi * u53(b.z, b.w);
       double tmin = theta - kTwoPi, tmax = theta;
       u32x4 sw{0, 0, 0, 0};
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kSlice) void k_elliptica
         slice_sincos(theta, &sn, &cs);
 #pragma unroll
         for (int k = 0; k < D; ++k)
-          y[k] = grad_selected<Model>(a.select, k) ? fma(nu[k], sn, fma(f[k], cs, mu[k])) : x[k];
+          y[k] = move_selected<Model>(a.select, k) ? fma(nu[k], sn, fma(f[k], cs, mu[k])) : x[k];
         const double ll2 = Model::loglik(p, o, y);
         if (ll2 - ll > logu) {
 #pragma unroll
@@ -213,12 +211,8 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kSlice) void k_elliptica
 #pragma unroll
     for (int k = 0; k < D; ++k) a.x[xidx(j, k, D)] = x[k];
   }
-  const uint64_t tot = wave_sum_u64((uint64_t)shr);
-  const uint64_t tex = wave_sum_u64((uint64_t)exh);
-  if ((threadIdx.x & 63) == 0) {
-    if (tot) atomicAdd(a.accepted, (unsigned long long)tot);
-    if (tex) atomicAdd(exhausted, (unsigned long long)tex);
-  }
+  move_count(a.accepted, shr);
+  move_count(exhausted, exh);
 }
 
 // map_optimize on every particle, a.n_moves iterations; a.accepted counts the
@@ -239,7 +233,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kMap) void k_map_optimiz
     typename G::Ctx c;
     {
       double xp[D];
-      grad_load<D, INIT>(a, j, x, xp);
+      move_load<D, INIT>(a, j, x, xp);
       G::prep(p, o, a.t, xp, c);
     }
     double s = G::eval(p, o, a.t, c, x, g);
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kMap) void k_map_optimiz
       double step = max_step;
       for (int b = 0; b < kMapMaxBacktracks; ++b) {
 #pragma unroll
-        for (int k = 0; k < D; ++k) y[k] = grad_selected<Model>(a.select, k) ? fma(step, g[k], x[k]) : x[k];
+        for (int k = 0; k < D; ++k) y[k] = move_selected<Model>(a.select, k) ? fma(step, g[k], x[k]) : x[k];
         const double s2 = G::eval(p, o, a.t, c, y, gy);
         if (s2 - s >= 0.0) {
 #pragma unroll
@@ -266,8 +260,7 @@ __global__ __launch_bounds__(kBlock, SliceWaves<Model>::kMap) void k_map_optimiz
 #pragma unroll
     for (int k = 0; k < D; ++k) a.x[xidx(j, k, D)] = x[k];
   }
-  const uint64_t tot = wave_sum_u64((uint64_t)imp);
-  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(a.accepted, (unsigned long long)tot);
+  move_count(a.accepted, imp);
 }
 
 }  // namespace gh
