@@ -2201,10 +2201,11 @@ static void log_raw_obs(gh_pf* pf, int t, const gh_obs* obs) {
 }
 
 // a slot model's logged step (log_raw_obs) as a gh_obs chain again, in
-// chain[0..kMaxSlots) (nullptr: nothing observed)
+// chain[0..kMaxSlots]: every slot and the step's input, make_obs_slots' limit
+// (nullptr: nothing observed)
 static const gh_obs* slot_chain(const std::vector<double>& r, gh_obs* chain) {
   int k = 0;
-  for (size_t i = 0; i + 1 < r.size() && k < kMaxSlots; ++k) {
+  for (size_t i = 0; i + 1 < r.size() && k < kMaxSlots + 1; ++k) {
     const int nv = (int)r[i + 1];
     chain[k] = gh_obs{};
     chain[k].values = r.data() + i + 2;
@@ -3334,7 +3335,7 @@ static int step_params_impl(gh_pf* pf, const gh_obs* obs, int proposal, gh_model
   for (int s = 1; s <= T; ++s) {
     const auto& r = pf->raw_obs[s - 1];
     if (m->family == GH_FAMILY_SLOTS) {
-      gh_obs chain[kMaxSlots];
+      gh_obs chain[kMaxSlots + 1];
       CHECK(make_obs(nm, s, slot_chain(r, chain), &rebuilt[s - 1]));
       continue;
     }

@@ -316,8 +316,9 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // without rescaling; thread 0 stores the block's triple.  Safe to call in a
 // loop on the same `sm`: sm[0] is read before the second barrier, sm[1..2]
 // (thread 0) before thread 0 reaches the next call's first barrier.
-__device__ __forceinline__ void block_partial(double lw, double (*sm)[4], double* pm, double* ps, double* ps2) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+// (lane, w, t0: the caller's lane, wave and thread-0 test — see makes_calls)
+__device__ __forceinline__ void block_partial(double lw, double (*sm)[4], double* pm, double* ps, double* ps2,
+                                              int lane, int w, bool t0) {
   const double mw = wave_max(lw);
   if (lane == 0) sm[0][w] = mw;
   lds_barrier();
@@ -331,11 +332,14 @@ __device__ __forceinline__ void block_partial(double lw, double (*sm)[4], double
     sm[2][w] = s2w;
   }
   lds_barrier();
-  if (threadIdx.x == 0) {
+  if (t0) {
     *pm = mb;
     *ps = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
     *ps2 = (sm[2][0] + sm[2][1]) + (sm[2][2] + sm[2][3]);
   }
+}
+__device__ __forceinline__ void block_partial(double lw, double (*sm)[4], double* pm, double* ps, double* ps2) {
+  block_partial(lw, sm, pm, ps, ps2, threadIdx.x & 63, threadIdx.x >> 6, threadIdx.x == 0);
 }
 
 // The rank maximum of a max_only step, folded by the step kernel itself:
@@ -358,18 +362,42 @@ __host__ __device__ __forceinline__ double amax_value(uint64_t k) {
 // Block maximum only (the fused resample computes the weight sums in its own
 // pass over the log-weights, where it evaluates exp(w - M) anyway).
 __device__ __forceinline__ void block_max_partial(double lw, double (*sm)[4], double* pm, uint64_t* amax,
-                                                  int64_t vb) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+                                                  int64_t vb, int lane, int w, bool t0) {
   const double mw = wave_max(lw);
   if (lane == 0) sm[0][w] = mw;
   lds_barrier();
-  if (threadIdx.x == 0) {
+  if (t0) {
     const double mb = fmax(fmax(sm[0][0], sm[0][1]), fmax(sm[0][2], sm[0][3]));
     *pm = mb;
     if (amax)
       __hip_atomic_fetch_max(&amax[(vb & (kAmaxShards - 1)) * kAmaxStride], amax_key(mb), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+__device__ __forceinline__ void block_max_partial(double lw, double (*sm)[4], double* pm, uint64_t* amax,
+                                                  int64_t vb) {
+  block_max_partial(lw, sm, pm, amax, vb, threadIdx.x & 63, threadIdx.x >> 6, threadIdx.x == 0);
+}
+
+// For a model whose step makes out-of-line calls (Model::kCalls: the extended
+// slot instantiations) the block fold reads nothing that a vector register
+// carried across the call (the stores of the state and the weight still use j,
+// lane and tile from before it).  In k_step<SlotModel<16, true>, false> the
+// compiler kept threadIdx.x for the block fold in a register that it copied at
+// the head of a join block, before that block restored exec: the lanes that
+// had skipped the branch came back from the call with a stale thread index, no
+// thread passed the thread-0 test and the block's maximum was never stored
+// (DESIGN.md §5).
+// For such a model the wave index is held in a scalar register (copied whole,
+// whatever exec is) and the lane is counted again after the step.
+template <class M, class = void>
+struct makes_calls : std::false_type {};
+template <class M>
+struct makes_calls<M, std::void_t<decltype(M::kCalls)>> : std::bool_constant<M::kCalls> {};
+__device__ __forceinline__ int lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
 }
 
 // One particle per lane, 64-particle tiles per wave, 4 waves per block, one
@@ -396,6 +424,7 @@ __global__ __launch_bounds__(kBlock, Model::kMinWaves) void k_step(const double*
   // arguments made every other launch's waves wait for them before their
   // first loads — k_step 35.6 -> 37.5 us, A/B on one box)
   const int64_t vb = SPLIT ? (int64_t)blockIdx.x + (blockIdx.x >= a.vb_split ? a.vb_skip : 0) : (int64_t)blockIdx.x;
+  const int ws = makes_calls<Model>::value ? __builtin_amdgcn_readfirstlane(w) : w;  // (see makes_calls)
   const int64_t tile = vb * (kBlock / 64) + w;
   const int64_t j = tile * 64 + lane;
   // The device flags and this slot's range mark + carry are loaded before the
@@ -486,8 +515,15 @@ __global__ __launch_bounds__(kBlock, Model::kMinWaves) void k_step(const double*
       a.logw[j] = lw;
     }
   }
-  if (a.max_only) block_max_partial(lw, sm, a.pm + vb, a.amax, vb);
-  else block_partial(lw, sm, a.pm + vb, a.ps + vb, a.ps2 + vb);
+  if constexpr (makes_calls<Model>::value) {
+    const int fl = lane_now();
+    const bool t0 = fl == 0 && ws == 0;
+    if (a.max_only) block_max_partial(lw, sm, a.pm + vb, a.amax, vb, fl, ws, t0);
+    else block_partial(lw, sm, a.pm + vb, a.ps + vb, a.ps2 + vb, fl, ws, t0);
+  } else {
+    if (a.max_only) block_max_partial(lw, sm, a.pm + vb, a.amax, vb);
+    else block_partial(lw, sm, a.pm + vb, a.ps + vb, a.ps2 + vb);
+  }
 }
 
 // k_step for one-dimensional models whose particles p, p + 64 share their

@@ -193,6 +193,7 @@ template <int D, bool EXT = false>
 struct SlotModel {
   static constexpr int kD = D;
   static constexpr int kMinWaves = D <= 3 ? 8 : (D <= 6 ? 6 : (D <= 10 ? 4 : 3));
+  static constexpr bool kCalls = EXT;  // out-of-line library calls in the step (gh_kernels.h makes_calls)
   using Params = SlotParams;
 
   // c + h.x (fma over the components ascending)
@@ -600,6 +601,7 @@ template <int D, bool EXT = false>
 struct SlotLinModel {
   static constexpr int kD = D;
   static constexpr int kMinWaves = SlotModel<D, EXT>::kMinWaves;
+  static constexpr bool kCalls = EXT;
   using Params = SlotParams;
   using Prior = SlotModel<D, EXT>;
 
