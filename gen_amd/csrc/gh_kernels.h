@@ -303,6 +303,36 @@ __device__ __forceinline__ void buf_st_f64x2(const double* in, __amdgpu_buffer_r
   __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, (int)soff, 0);
 }
 
+// LDS-DMA: 16 bytes per lane from the buffer straight into LDS, lane l's at
+// lds + imm + 16 l (lds wave-uniform; `buffer_load_dwordx4 ... offen lds`).
+// The immediate offset moves both the source and the destination.  No
+// destination registers: the data is in LDS once the wave's vmcnt says so.
+template <int IMM>
+__device__ __forceinline__ void buf_ld_lds_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t voff, void* lds) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, 0, IMM, 0);
+}
+// component pairs 0 .. P-1 of a wave tile's particles (voff: the lane's offset
+// of pair 0) into P KiB of LDS, pair c at c KiB
+template <int P, int C = 0>
+__device__ __forceinline__ void stage_pairs(__amdgpu_buffer_rsrc_t r, uint32_t voff, void* lds) {
+  if constexpr (C < P) {
+    buf_ld_lds_f64x2<C * kTileP * 16>(r, voff, lds);
+    stage_pairs<P, C + 1>(r, voff, lds);
+  }
+}
+
+// A model opts into the step kernel's LDS-staged gather with kLdsPairs (the
+// component pairs that go through LDS) and kStepWaves (the occupancy target
+// of that instantiation, k_step<Model, false, false>).
+template <class M, class = void>
+struct lds_pairs : std::integral_constant<int, 0> {};
+template <class M>
+struct lds_pairs<M, std::void_t<decltype(M::kLdsPairs)>> : std::integral_constant<int, M::kLdsPairs> {};
+template <class M, bool INIT, bool SPLIT, class = void>
+struct step_waves : std::integral_constant<int, M::kMinWaves> {};
+template <class M>
+struct step_waves<M, false, false, std::void_t<decltype(M::kStepWaves)>> : std::integral_constant<int, M::kStepWaves> {};
+
 // ---------------------------------------------------------------- k_step
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
 // accesses (lgkmcnt) but not for its global stores, so the states a wave has
@@ -412,10 +442,11 @@ __device__ __forceinline__ int lane_now() {
 // the memory side), and the block barrier waits for LDS only, so a block's
 // state stores are not waited for before it retires.
 template <class Model, bool INIT, bool SPLIT = false>
-__global__ __launch_bounds__(kBlock, Model::kMinWaves) void k_step(const double* __restrict__ prm,
-                                                                    typename Model::Params p0, StepObs o,
-                                                                    StepArgs a) {
+__global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) void k_step(
+    const double* __restrict__ prm, typename Model::Params p0, StepObs o, StepArgs a) {
   constexpr int D = Model::kD;
+  constexpr int P = (INIT || SPLIT) ? 0 : lds_pairs<Model>::value;  // pairs of x_{t-1} staged in LDS
+  static_assert(P <= D / 2, "kLdsPairs counts whole component pairs");
   const typename Model::Params p = p0.rebase(prm);
   __shared__ double sm[3][4];
   __shared__ double logtab[kMathTabDoubles];
@@ -470,6 +501,38 @@ __global__ __launch_bounds__(kBlock, Model::kMinWaves) void k_step(const double*
       double x[D];
       if (INIT) {
         lw = Model::init(p, o, a.seed, (uint64_t)(a.lo + j), a.proposal, x, dr_init);
+      } else if constexpr (P > 0) {
+        // The LDS-staged gather: the first P pairs go by LDS-DMA into this
+        // wave's P KiB (pair c of lane l at c KiB + 16 l: ds_read_b128 without
+        // bank conflicts), the others into registers as below; the model reads
+        // the staged pairs after its draws (StagedPrev).  Wave-private data: no
+        // block barrier.  The general path stages its first P pairs itself
+        // (it has waited for them), so one step sequence serves both.
+        __shared__ gh_v4u xstage[kBlock / 64][P][kTileP];
+        gh_v4u* const st = &xstage[w][0][0];
+        StagedPrev<D, P> xs;
+        xs.lds = reinterpret_cast<const double*>(st + lane);
+        if (pend && !use_marks) src = a.anc[j];
+        if (a.buf && __builtin_amdgcn_ballot_w64(src < 0) == 0) {
+          const __amdgpu_buffer_rsrc_t rp = gh_rsrc(a.xprev);
+          const uint32_t tb = ((uint32_t)src >> 6) * (uint32_t)(kTileP * D * 8), l = (uint32_t)src & 63u;
+          stage_pairs<P>(rp, tb + l * 16u, st);
+#pragma unroll
+          for (int c = P; c < D / 2; ++c) buf_ld_f64x2(rp, tb + l * 16u, (uint32_t)(c * kTileP * 16), &xs.r[2 * c]);
+          if (D & 1) xs.r[D - 1] = buf_ld_f64(rp, tb + l * 8u, (uint32_t)((D - 1) * kTileP * 8));
+        } else {
+          const bool loc = src >= 0;
+#pragma unroll
+          for (int k = 0; k < D; ++k)
+            xs.r[k] = loc ? a.xprev[xidx(src, k, D)] : ld_sys(&a.remote[(-1 - src) * a.ld_remote + k]);
+#pragma unroll
+          for (int c = 0; c < P; ++c) {
+            const uint64_t u = as_u64(xs.r[2 * c]), v = as_u64(xs.r[2 * c + 1]);
+            st[c * kTileP + lane] = gh_v4u{(unsigned)u, (unsigned)(u >> 32), (unsigned)v, (unsigned)(v >> 32)};
+          }
+        }
+        const double inc = Model::step(p, o, a.seed, (uint64_t)(a.lo + j), a.t, a.proposal, xs, x, dr_step);
+        lw = (pend ? 0.0 : a.logw[j]) + inc;
       } else {
         double xp[D];
         if (pend && !use_marks) src = a.anc[j];

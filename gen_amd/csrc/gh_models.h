@@ -95,6 +95,36 @@ struct LGParams {
   }
 };
 
+// x_{t-1} of a step whose first P component pairs wait in LDS (k_step's
+// LDS-staged gather, Model::kLdsPairs): the pairs were sent there by LDS-DMA
+// loads, which hold no destination registers while the normals are drawn; the
+// model reads them where its mat-vec consumes them.  The region is private to
+// the wave (pair c of this lane at lds[c * 128]), so the DMA's vmcnt wait is
+// all that orders the reads.
+template <int D, int P>
+struct StagedPrev {
+  const double* lds;  // this lane's pair 0
+  double r[D];        // components 2P .. D-1 (the first 2P are not used)
+  __device__ __forceinline__ void get(double* xp) const {
+    // the compiler does not count the DMA loads: wait for them here (they were
+    // issued before the register pairs' loads, which the mat-vec needs with
+    // them, so the full wait costs nothing; nothing may be read before it)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int c = 0; c < P; ++c) {
+      const double2 v = *reinterpret_cast<const double2*>(lds + c * 128);
+      xp[2 * c] = v.x;
+      xp[2 * c + 1] = v.y;
+    }
+#pragma unroll
+    for (int k = 2 * P; k < D; ++k) xp[k] = r[k];
+  }
+};
+
+#if !defined(GH_LG10_LDS_PAIRS)  // timing-only variants set it (0: the register gather)
+#define GH_LG10_LDS_PAIRS 3
+#endif
+
 // S: structure known at model-compile time (host detects exact zeros):
 //   bit 0 — chol(Q) is diagonal:   L z needs only the diagonal terms
 //   bit 1 — L_R^{-1} H is diagonal (dy == d): the residual needs only x_r
@@ -109,6 +139,18 @@ struct LGModel {
 #else
   static constexpr int kMinWaves =
       (D <= 3) ? 8 : (D <= 5 ? 7 : (D < 10 ? (S == 3 && D != 7 && D != 9 ? 6 : 5) : (D == 10 ? (S == 3 ? 7 : 5) : 4)));
+#endif
+  // k_step<.., false, false> only (the init and split-step instantiations keep
+  // kMinWaves): component pairs of x_{t-1} gathered through LDS-DMA
+  // (StagedPrev), and that instantiation's occupancy target.  d = 10 diagonal:
+  // with 3 of the 5 pairs out of the registers during the draws the kernel fits
+  // 64 VGPRs without scratch (2 pairs: 7 spills; none: 12), and its 18.5 KB of
+  // LDS fit 8 blocks per CU.
+  static constexpr int kLdsPairs = (D == 10 && S == 3) ? GH_LG10_LDS_PAIRS : 0;
+#if defined(GH_LG10_WAVES)
+  static constexpr int kStepWaves = kMinWaves;
+#else
+  static constexpr int kStepWaves = kLdsPairs > 0 ? 8 : kMinWaves;
 #endif
   using Params = LGParams;
 
@@ -220,6 +262,25 @@ struct LGModel {
                                 Draw dr = {STREAM_STEP, 0}) {
     double z[D + 1];
     normals_n<D>(seed, pid, t, dr.stream, dr.base, z, dr.tab);
+    return step_mean_noise(p, o, xp, z, x);
+  }
+
+  // the same with x_{t-1} partly staged in LDS: the staged pairs are read
+  // after the draws (the same values, the same operations)
+  template <int P>
+  __device__ static double step(const Params& p, const StepObs& o, uint64_t seed, uint64_t pid,
+                                uint32_t t, int /*proposal*/, const StagedPrev<D, P>& xs, double* x,
+                                Draw dr = {STREAM_STEP, 0}) {
+    double z[D + 1];
+    normals_n<D>(seed, pid, t, dr.stream, dr.base, z, dr.tab);
+    double xp[D];
+    xs.get(xp);
+    return step_mean_noise(p, o, xp, z, x);
+  }
+
+  // x = A xp + b + L_Q z and the observation's logpdf
+  __device__ __forceinline__ static double step_mean_noise(const Params& p, const StepObs& o, const double* xp,
+                                                           const double* z, double* x) {
 #pragma unroll
     for (int i = 0; i < D; ++i) {
       double acc = p.b[i];

@@ -12,8 +12,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 VARIANTS = {
     "base": [],
-    "occ8": ["GH_LG10_WAVES=8"],
-    "occ6": ["GH_LG10_WAVES=6"],
+    "occ8": ["GH_LG10_WAVES=8", "GH_LG10_LDS_PAIRS=0"],
+    "occ6": ["GH_LG10_WAVES=6", "GH_LG10_LDS_PAIRS=0"],
+    # the step kernel's LDS-staged gather: lds0 is the register
+    # gather at 7 waves per SIMD, lds3w7 the staged gather held at 7 waves
+    "lds0": ["GH_LG10_LDS_PAIRS=0"],
+    "lds3w7": ["GH_LG10_WAVES=7"],
     "philox1": ["GH_PHILOX_ROUNDS=1"],
     "philox7": ["GH_PHILOX_ROUNDS=7"],
     "coal_w10": ["GH_COAL_WIN=10"],
