@@ -24,17 +24,26 @@ constexpr int kScanTile = kBlock * kScanItems;   // particles per CDF block
 
 // Wave-tiled state slots: the states of one step are stored in
 // 64-particle tiles, a tile's D components one contiguous run of 64·D
-// doubles: component pairs (2c, 2c+1) interleaved per particle, [D/2][64][2],
-// then for odd D the last component as a plain [64] column — component k of
-// particle i at xidx(i, k, D).  A lane reads or writes a component pair as one
-// 16-byte word (a wave: 1 KiB contiguous).  (The column-major [D][n] layout
-// put a particle's D components n·8 bytes apart — 8 MiB at 2^20 — and its
-// gather+store skeleton ran 14 % slower through HBM; 8-byte words per
-// component 3 % slower: tools/ubench_layout.hip.)
+// doubles — component k of particle i at xidx(i, k, D) — in one of two forms.
+// Pair tiles: component pairs (2c, 2c+1) interleaved per particle,
+// [D/2][64][2], then for odd D the last component as a plain [64] column.  A
+// lane reads or writes a component pair as one 16-byte word (a wave: 1 KiB
+// contiguous).  (The column-major [D][n] layout put a particle's D components
+// n·8 bytes apart — 8 MiB at 2^20 — and its gather+store skeleton ran 14 %
+// slower through HBM; 8-byte words per component 3 % slower.)
+// Row tiles (state_rows(D): d = 10): [64][D], a particle's D components one
+// contiguous row of 8·D bytes.  After a resample a step reads only the
+// surviving ancestors' states; a 128-byte line of a pair tile holds one pair
+// of 8 consecutive particles, so nearly every line of x_{t-1} is fetched
+// though most particles are dead, and rows fetch 0.44 instead of 0.74 of the
+// slot on the bench's run.  The step kernel transposes its stores through LDS
+// so that each still writes whole lines (tools/ubench_layout.hip).
 constexpr int kTileP = 64;
+__host__ __device__ constexpr bool state_rows(int D) { return D == 10; }
 __host__ __device__ __forceinline__ int64_t tbase(int64_t i, int D) { return (i >> 6) * (int64_t)(kTileP * D); }
 __host__ __device__ __forceinline__ int64_t xidx(int64_t i, int k, int D) {
   const int l = (int)(i & 63);
+  if (state_rows(D)) return tbase(i, D) + l * D + k;
   return tbase(i, D) + (k < (D & ~1) ? (k >> 1) * (2 * kTileP) + 2 * l + (k & 1) : (D - 1) * kTileP + l);
 }
 __host__ __device__ __forceinline__ int64_t slot_doubles(int64_t n, int D) {
@@ -321,6 +330,52 @@ __device__ __forceinline__ void stage_pairs(__amdgpu_buffer_rsrc_t r, uint32_t v
   }
 }
 
+// the same from row tiles (voff: the lane's row): pair c comes from 16 c bytes
+// into the row (the scalar offset moves the source alone) and goes to c KiB
+template <int P, int C = 0>
+__device__ __forceinline__ void stage_row_pairs(__amdgpu_buffer_rsrc_t r, uint32_t voff, gh_v4u* lds) {
+  if constexpr (C < P) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(lds + C * kTileP), 16,
+                                             (int)voff, C * 16, 0, 0);
+    stage_row_pairs<P, C + 1>(r, voff, lds);
+  }
+}
+
+// The state store of a row-tiled step (state_rows): the wave's 64 rows are
+// 5 KiB contiguous, but a lane holds one row, and stores straight from the
+// lanes would touch 40 lines partially per instruction (35.3 against 26.0 us
+// in the skeleton, tools/ubench_layout.hip).  So the rows go through `stg`
+// (kRowStageWords 16-byte words of LDS private to the wave) in two passes of 32
+// rows = 20 whole lines: the lanes of that half write their row, then lane l
+// stores words l, 64 + l and 128 + l of the pass's 160 in image order.  Every
+// lane of the wave takes part; row r is stored iff bit r of `live` is set (the
+// lanes whose x is valid: masked by row, not by lane).  One wave's LDS
+// operations execute in order; the waits keep the compiler from moving them.
+constexpr int kRowStageWords = 32 * 10 / 2;
+template <int D>
+__device__ __forceinline__ void store_rows_staged(const double* x, bool valid, uint64_t live, gh_v4u* stg,
+                                                  __amdgpu_buffer_rsrc_t ro, uint32_t tb, int lane) {
+  static_assert(D == 10, "two passes of 32 rows of 5 words");
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the region's earlier reads
+    if (valid && (lane >> 5) == h) {
+#pragma unroll
+      for (int c = 0; c < D / 2; ++c) {
+        const uint64_t u = as_u64(x[2 * c]), v = as_u64(x[2 * c + 1]);
+        stg[(lane & 31) * (D / 2) + c] = gh_v4u{(unsigned)u, (unsigned)(u >> 32), (unsigned)v, (unsigned)(v >> 32)};
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      const int W = m * 64 + lane;  // word W of the pass: word W % 5 of row 32 h + W / 5
+      if (W < kRowStageWords && ((live >> (32 * h + W / (D / 2))) & 1))
+        __builtin_amdgcn_raw_buffer_store_b128(stg[W], ro, (int)(tb + (uint32_t)(h * kRowStageWords + W) * 16u), 0, 0);
+    }
+  }
+}
+
 // A model opts into the step kernel's LDS-staged gather with kLdsPairs (the
 // component pairs that go through LDS) and kStepWaves (the occupancy target
 // of that instantiation, k_step<Model, false, false>).
@@ -447,10 +502,23 @@ __global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) vo
   constexpr int D = Model::kD;
   constexpr int P = (INIT || SPLIT) ? 0 : lds_pairs<Model>::value;  // pairs of x_{t-1} staged in LDS
   static_assert(P <= D / 2, "kLdsPairs counts whole component pairs");
+  // row tiles: the state store is transposed through LDS (store_rows_staged).
+  // Not for a model that makes calls, whose lanes' indices are not to be
+  // trusted after them (makes_calls above), and not in the split step's part
+  // 2, which runs the few tiles that hold received rows (and spilled two
+  // registers with it): these write their rows straight from the lanes.
+  constexpr bool RSTG = state_rows(D) && !makes_calls<Model>::value && !SPLIT;
+  constexpr int kStageWords = P > 0 ? P * kTileP : (RSTG ? kRowStageWords : 0);  // per wave
+  static_assert(!RSTG || kStageWords >= kRowStageWords, "the store is staged in the gather's region");
   const typename Model::Params p = p0.rebase(prm);
   __shared__ double sm[3][4];
   __shared__ double logtab[kMathTabDoubles];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  gh_v4u* stg0 = nullptr;  // the waves' staging regions (the gather's pairs, then the row store)
+  if constexpr (kStageWords > 0) {
+    __shared__ gh_v4u xstage[kBlock / 64][kStageWords];
+    stg0 = &xstage[0][0];
+  }
   // (the remap lives in its own instantiation: the compare on two kernel
   // arguments made every other launch's waves wait for them before their
   // first loads — k_step 35.6 -> 37.5 us, A/B on one box)
@@ -497,8 +565,14 @@ __global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) vo
     }
     // part 1 of a split multi-rank step: slots that take a received row are
     // stepped by part 2 once the rows have landed (no read of rows_recv here)
+    // (the staged row store reads x after the branch, from every lane that set
+    // act; otherwise x lives inside the branch, as the compiler saw it before)
+    double xo[RSTG ? D : 1];
+    bool act = false;
     if (j < a.n && !(a.part == 1 && src < 0)) {
-      double x[D];
+      double xi[RSTG ? 1 : D];
+      double* const x = RSTG ? xo : xi;
+      if constexpr (RSTG) act = true;
       if (INIT) {
         lw = Model::init(p, o, a.seed, (uint64_t)(a.lo + j), a.proposal, x, dr_init);
       } else if constexpr (P > 0) {
@@ -508,18 +582,24 @@ __global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) vo
         // the staged pairs after its draws (StagedPrev).  Wave-private data: no
         // block barrier.  The general path stages its first P pairs itself
         // (it has waited for them), so one step sequence serves both.
-        __shared__ gh_v4u xstage[kBlock / 64][P][kTileP];
-        gh_v4u* const st = &xstage[w][0][0];
+        gh_v4u* const st = stg0 + w * kStageWords;
         StagedPrev<D, P> xs;
         xs.lds = reinterpret_cast<const double*>(st + lane);
         if (pend && !use_marks) src = a.anc[j];
         if (a.buf && __builtin_amdgcn_ballot_w64(src < 0) == 0) {
           const __amdgpu_buffer_rsrc_t rp = gh_rsrc(a.xprev);
+          if constexpr (state_rows(D)) {
+            const uint32_t rb = (uint32_t)src * (uint32_t)(D * 8);
+            stage_row_pairs<P>(rp, rb, st);
+#pragma unroll
+            for (int c = P; c < D / 2; ++c) buf_ld_f64x2(rp, rb, (uint32_t)(c * 16), &xs.r[2 * c]);
+          } else {
           const uint32_t tb = ((uint32_t)src >> 6) * (uint32_t)(kTileP * D * 8), l = (uint32_t)src & 63u;
           stage_pairs<P>(rp, tb + l * 16u, st);
 #pragma unroll
           for (int c = P; c < D / 2; ++c) buf_ld_f64x2(rp, tb + l * 16u, (uint32_t)(c * kTileP * 16), &xs.r[2 * c]);
           if (D & 1) xs.r[D - 1] = buf_ld_f64(rp, tb + l * 8u, (uint32_t)((D - 1) * kTileP * 8));
+          }
         } else {
           const bool loc = src >= 0;
 #pragma unroll
@@ -545,10 +625,16 @@ __global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) vo
         // multi-rank step cost k_step 37 -> 44 us at world 1 (round 5)
         if (a.buf && __builtin_amdgcn_ballot_w64(src < 0) == 0) {  // local rows, slots < 4 GiB: 16-byte buffer loads of component pairs
           const __amdgpu_buffer_rsrc_t rp = gh_rsrc(a.xprev);
+          if constexpr (state_rows(D)) {
+            const uint32_t rb = (uint32_t)src * (uint32_t)(D * 8);
+#pragma unroll
+            for (int c = 0; c < D / 2; ++c) buf_ld_f64x2(rp, rb, (uint32_t)(c * 16), &xp[2 * c]);
+          } else {
           const uint32_t tb = ((uint32_t)src >> 6) * (uint32_t)(kTileP * D * 8), l = (uint32_t)src & 63u;
 #pragma unroll
           for (int c = 0; c < D / 2; ++c) buf_ld_f64x2(rp, tb + l * 16u, (uint32_t)(c * kTileP * 16), &xp[2 * c]);
           if (D & 1) xp[D - 1] = buf_ld_f64(rp, tb + l * 8u, (uint32_t)((D - 1) * kTileP * 8));
+          }
         } else {  // general: a local tile (xidx) or a received row (stride 1)
           const bool loc = src >= 0;
 #pragma unroll
@@ -565,17 +651,35 @@ __global__ __launch_bounds__(kBlock, (step_waves<Model, INIT, SPLIT>::value)) vo
         lw = (pend ? 0.0 : a.logw[j]) + inc;
       }
 
-      if (a.buf) {
+      if (RSTG && a.buf) {
+        // (stored below, by every lane of the wave)
+      } else if (a.buf) {
         const __amdgpu_buffer_rsrc_t ro = gh_rsrc(a.xout);
         const uint32_t tb = (uint32_t)tile * (uint32_t)(kTileP * D * 8);
+        if constexpr (state_rows(D)) {  // rows straight from the lanes
+#pragma unroll
+          for (int c = 0; c < D / 2; ++c) buf_st_f64x2(&x[2 * c], ro, tb + (uint32_t)lane * (uint32_t)(D * 8), (uint32_t)(c * 16));
+        } else {
 #pragma unroll
         for (int c = 0; c < D / 2; ++c) buf_st_f64x2(&x[2 * c], ro, tb + (uint32_t)lane * 16u, (uint32_t)(c * kTileP * 16));
         if (D & 1) buf_st_f64(x[D - 1], ro, tb + (uint32_t)lane * 8u, (uint32_t)((D - 1) * kTileP * 8));
+        }
       } else {
 #pragma unroll
         for (int k = 0; k < D; ++k) a.xout[xidx(j, k, D)] = x[k];
       }
       a.logw[j] = lw;
+    }
+    if constexpr (RSTG) {
+      if (a.buf) {
+        // (the gather's staged inputs are dead: x is computed from them; the
+        // region's address is computed again from the thread index, so that no
+        // register holds it across the step)
+        int t2 = threadIdx.x;
+        asm volatile("" : "+v"(t2));
+        store_rows_staged<D>(xo, act, __builtin_amdgcn_ballot_w64(act), stg0 + (t2 >> 6) * kStageWords, gh_rsrc(a.xout),
+                             (uint32_t)tile * (uint32_t)(kTileP * D * 8), t2 & 63);
+      }
     }
   }
   if constexpr (makes_calls<Model>::value) {

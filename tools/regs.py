@@ -29,4 +29,4 @@ for r in rows:
     if filt and not any(f in r["name"] for f in filt):
         continue
     print(f"{r['name'][:70]:70s} vgpr={r.get('VGPRs')} sgpr={r.get('TotalSGPRs')} occ={r.get('Occupancy [waves/SIMD]')} "
-          f"vspill={r.get('VGPRs Spill')} scratch={r.get('ScratchSize [bytes/lane]')}")
+          f"vspill={r.get('VGPRs Spill')} scratch={r.get('ScratchSize [bytes/lane]')} lds={r.get('LDS Size [bytes/block]')}")
