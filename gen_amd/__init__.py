@@ -35,6 +35,11 @@ from .pf import (
     hmc,
     elliptical_slice,
     map_optimize,
+    ParticleEstimate,
+    estimate,
+    effective_sample_size,
+    weighted_mean,
+    weighted_covariance,
     gaussian_drift,
     GaussianDriftProposal,
     mh,
@@ -60,4 +65,5 @@ __all__ = [
     "particle_gibbs", "GenHipError", "ObservationBatch", "prepare_observations", "Selection", "select",
     "metropolis_hastings", "mh", "simulate", "SimulatedTraces", "dists", "gaussian_drift", "GaussianDriftProposal",
     "choice_gradients", "mala", "hmc", "elliptical_slice", "map_optimize",
+    "ParticleEstimate", "estimate", "effective_sample_size", "weighted_mean", "weighted_covariance",
 ]

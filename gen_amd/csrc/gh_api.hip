@@ -30,6 +30,7 @@
 #include "gh_rejuv.h"
 #include "gh_csmc.h"
 #include "gh_inst.h"
+#include "gh_moments.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
 
@@ -65,6 +66,7 @@ GH_SLICE_UNIT3(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT4(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT5(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT6(GH_EXTERN_TEMPLATE)
+GH_EST_UNIT(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1349,6 +1351,12 @@ struct gh_pf {
   bool cond = false;
   double* pin = nullptr;          // [D] this step's distinguished state, [D] its new log weight
   std::vector<void*> chunks;      // history allocations (record_history)
+  // gh_pf_estimate's scratch, allocated at its first use: the result block
+  // (+ W), the block partials and the per-step ancestor pointers of a walk
+  double* est_res = nullptr;
+  double* est_part = nullptr;
+  const int32_t** est_ancs = nullptr;
+  int est_ancs_cap = 0;
   // kernel timing
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -1519,6 +1527,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->mn_key); hipFree(pf->mn_pos); hipFree(pf->mn_anc); hipFree(pf->mn_bcnt); hipFree(pf->mn_boff);
   hipFree(pf->acc_count); hipFree(pf->exh_count); hipFree(pf->pin); hipFree(pf->amax);
   hipFree(pf->amax_all); hipFree(pf->rec); hipFree(pf->recs_all); hipFree(pf->qlin);
+  hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
   if (pf->ev_plan) hipEventDestroy(pf->ev_plan);
@@ -3193,6 +3202,104 @@ extern "C" int gh_pf_get_trajectory(gh_pf* pf, int t, double* out) {
   hipFree(dout);
   hipFree(dxs);
   hipFree(dancs);
+  return GH_OK;
+}
+
+// ------------------------------------------------ estimates on the device
+// effective_sample_size / normalize_weights (particle_filter.jl:3-14) and the
+// weighted mean and covariance callers take over get_traces with
+// get_log_weights, reduced where the particles are (gh_moments.h): at most
+// 1 + d + d^2 doubles leave the device, after one stream synchronise.
+template <int D>
+static void launch_est(gh_pf* pf, const EstArgs& a, unsigned nb, bool cov) {
+  if (cov)
+    hipLaunchKernelGGL(k_est_cov<D>, dim3(nb, est_panels(D)), dim3(kBlock), 0, pf->s, a);
+  else
+    hipLaunchKernelGGL(k_est_mean<D>, dim3(nb), dim3(kBlock), 0, pf->s, a);
+}
+
+static int est_pass(gh_pf* pf, const EstArgs& a, unsigned nb, bool cov) {
+  if (cov) nb = std::min<unsigned>(nb, kEstCovBlocks);
+  switch (pf->D) {
+#define GH_EST_CASE(D) case D: launch_est<D>(pf, a, nb, cov); break;
+    GH_EST_CASE(1) GH_EST_CASE(2) GH_EST_CASE(3) GH_EST_CASE(4) GH_EST_CASE(5) GH_EST_CASE(6) GH_EST_CASE(7)
+    GH_EST_CASE(8) GH_EST_CASE(9) GH_EST_CASE(10) GH_EST_CASE(11) GH_EST_CASE(12) GH_EST_CASE(13) GH_EST_CASE(14)
+    GH_EST_CASE(15) GH_EST_CASE(16)
+#undef GH_EST_CASE
+    default: return set_err(GH_E_INVAL, "gh_pf_estimate: no kernel for a latent of %d components", pf->D);
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_est_fold, dim3(1), dim3(1024), 0, pf->s, (const double*)pf->est_part, (int)nb, pf->D,
+                     cov ? 1 : 0, pf->est_res);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
+extern "C" int gh_pf_estimate(gh_pf* pf, int t, double* ess, double* mean, double* cov) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  if (!ess && !mean && !cov) return set_err(GH_E_INVAL, "gh_pf_estimate: ess, mean and cov are all null");
+  const int T = pf->t, D = pf->D;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_estimate before init");
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "gh_pf_estimate: not for a filter sharded over ranks (the multi-rank path)");
+  if (t < 0 || t > T) return set_err(GH_E_INVAL, "step %d outside 1..%d", t, T);
+  if (t == 0) t = T;
+  if (!pf->opts.record_history && t != T)
+    return set_err(GH_E_STATE, "record_history is off: only the current step is kept");
+  if (D < 1 || D > 16) return set_err(GH_E_INVAL, "gh_pf_estimate: no kernel for a latent of %d components", D);
+  if (pf->n < 1) return set_err(GH_E_STATE, "gh_pf_estimate: no particles");
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  const bool states = mean || cov;
+  // the grid is a function of n only: a block of 4 waves per 4 tiles, at most kEstMaxBlocks
+  const int64_t tiles = (pf->n + kTileP - 1) / kTileP;
+  const unsigned nb = (unsigned)std::min<int64_t>((tiles + kBlock / 64 - 1) / (kBlock / 64), kEstMaxBlocks);
+  if (!pf->est_res) HIP_TRY(hipMalloc(&pf->est_res, sizeof(double) * (est_result_doubles(16) + 1)));
+  if (states && !pf->est_part)
+    HIP_TRY(hipMalloc(&pf->est_part, sizeof(double) * (size_t)est_entries(D) * nb));
+  std::vector<const int32_t*> ha;  // (alive until the synchronise below)
+  if (states && t != T) {
+    if (pf->est_ancs_cap < T) {
+      hipFree(pf->est_ancs);
+      pf->est_ancs = nullptr;
+      pf->est_ancs_cap = 0;
+      const int nc = std::max(pf->cap, T);
+      HIP_TRY(hipMalloc(&pf->est_ancs, sizeof(int32_t*) * (size_t)nc));
+      pf->est_ancs_cap = nc;
+    }
+    ha.resize(T);
+    for (int s = 1; s <= T; ++s) ha[s - 1] = anc_for_step(pf, s);
+    HIP_TRY(hipMemcpyAsync(pf->est_ancs, ha.data(), sizeof(int32_t*) * T, hipMemcpyHostToDevice, pf->s));
+  }
+  if (states) CHECK(materialize_marks(pf));
+  CHECK(ensure_stats(pf));
+  hipLaunchKernelGGL(k_est_ess, dim3(1), dim3(64), 0, pf->s, (const double*)pf->stats_all,
+                     (const DevScalars*)pf->dev, flags_live(pf), pf->n, pf->est_res);
+  HIP_TRY(hipGetLastError());
+  if (states) {
+    EstArgs a{};
+    a.x = slot_x(pf, t);
+    a.ancs = pf->est_ancs;
+    a.res_before = pf->res_hist;
+    a.anc_pending = pf->cap >= T + 1 ? anc_for_step(pf, T + 1) : nullptr;
+    a.logw = pf->logw;
+    a.stats = pf->stats_all;
+    a.dev = pf->dev;
+    a.n = pf->n;
+    a.t_target = t;
+    a.t_cur = T;
+    a.live = flags_live(pf);
+    a.part = pf->est_part;
+    a.res = pf->est_res;
+    CHECK(est_pass(pf, a, nb, false));
+    if (cov) CHECK(est_pass(pf, a, nb, true));
+  }
+  double h[est_result_doubles(16)];
+  const int count = cov ? est_result_doubles(D) : (states ? 1 + D : 1);
+  CHECK(d2h(pf, h, pf->est_res, sizeof(double) * count));
+  if (h[0] != h[0])
+    return set_err(GH_E_NUMERIC, "gh_pf_estimate: the log-weights are all -inf, or hold a NaN or +inf");
+  if (ess) *ess = h[0];
+  if (mean) memcpy(mean, h + 1, sizeof(double) * D);
+  if (cov) memcpy(cov, h + 1 + D, sizeof(double) * D * D);
   return GH_OK;
 }
 

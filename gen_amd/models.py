@@ -168,6 +168,24 @@ class LinearGaussianSSM(Model):
             P = P - K @ self.H @ P
         return float(ll)
 
+    def kalman_filter(self, ys) -> tuple[np.ndarray, np.ndarray]:
+        """The exact filtered posterior p(x_t | y_1..t) of every step by the same
+        recursion (host, numpy): (means [T, d], covs [T, d, d]).  The analytic
+        answer of `estimate`'s weighted mean and covariance for this model."""
+        mu, P = self.mu0.copy(), self.P0.copy()
+        means, covs = [], []
+        for t, y in enumerate(np.atleast_2d(ys)):
+            if t > 0:
+                mu = self.A @ mu + self.b
+                P = self.A @ P @ self.A.T + self.Q
+            S = self.H @ P @ self.H.T + self.R
+            K = P @ self.H.T @ np.linalg.inv(S)
+            mu = mu + K @ (y - (self.H @ mu + self.c))
+            P = P - K @ self.H @ P
+            means.append(mu)
+            covs.append(P)
+        return np.array(means), np.array(covs)
+
     def log_joint(self, xs, ys) -> float:
         """Score of a trace (Gen's `get_score`): log p(x_1..T, y_1..T) of one
         latent trajectory xs [T, d] and its observations (None = absent), the

@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import byref, c_double, c_int, c_int64, c_void_p
+from typing import NamedTuple
 
 import numpy as np
 
@@ -271,6 +272,11 @@ class ParticleFilterState:
         else:
             _lib.check(lib.gh_pf_get_trajectory(self.h, int(t), _lib.dptr(out)))
         return out.T.copy()
+
+    @property
+    def ess(self) -> float:
+        """The effective sample size of the current weights (on the device)."""
+        return effective_sample_size(self)
 
     def ess_history(self):
         T = self.t
@@ -649,6 +655,63 @@ def get_log_weights(state: ParticleFilterState) -> np.ndarray:
 
 def get_traces(state: ParticleFilterState) -> ParticleTraces:
     return ParticleTraces(state)
+
+
+class ParticleEstimate(NamedTuple):
+    """`estimate`'s result: the effective sample size, the weighted mean [d]
+    and the weighted population covariance [d, d] (None when not asked for)."""
+    ess: float
+    mean: np.ndarray
+    cov: np.ndarray | None
+
+
+def _estimate_step(state: ParticleFilterState, t) -> int:
+    """The C ABI's step argument (0: the current step), refused here when out of range."""
+    if t is None:
+        return 0
+    T = state.t
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 1 <= int(t) <= T:
+        raise _lib.GenHipError(1, f"step {t!r} outside 1..{T} (None: the current step)")
+    return int(t)
+
+
+def estimate(state: ParticleFilterState, t: int | None = None, cov: bool = True) -> ParticleEstimate:
+    """The filtered posterior's summary, reduced on the device (gh_pf_estimate):
+    with w_i the normalised weights (normalize_weights, particle_filter.jl:8-14)
+    and x_i the latent of step t (default: current) along particle i's
+    genealogy, ess = 1 / sum w_i^2 (effective_sample_size,
+    particle_filter.jl:3-6), mean = sum w_i x_i and cov = sum w_i (x_i - mean)
+    (x_i - mean)^T, the weighted population covariance (no Bessel correction).
+    The expectation a caller would take over get_traces with get_log_weights,
+    without copying either to the host.  cov=False skips the second pass over
+    the states.  One rank only."""
+    step = _estimate_step(state, t)
+    d = state.model.d
+    e = c_double()
+    mean = np.empty(d, dtype=np.float64)
+    c = np.empty((d, d), dtype=np.float64) if cov else None
+    _lib.check(_lib.load().gh_pf_estimate(state.h, step, byref(e), _lib.dptr(mean),
+                                          _lib.dptr(c) if c is not None else None))
+    return ParticleEstimate(e.value, mean, c)
+
+
+def effective_sample_size(state: ParticleFilterState) -> float:
+    """effective_sample_size of the current normalised weights
+    (particle_filter.jl:3-6), from the device's weight sums: no pass over the
+    particles, one double copied."""
+    e = c_double()
+    _lib.check(_lib.load().gh_pf_estimate(state.h, 0, byref(e), None, None))
+    return e.value
+
+
+def weighted_mean(state: ParticleFilterState, t: int | None = None) -> np.ndarray:
+    """`estimate(state, t, cov=False).mean`."""
+    return estimate(state, t, cov=False).mean
+
+
+def weighted_covariance(state: ParticleFilterState, t: int | None = None) -> np.ndarray:
+    """`estimate(state, t).cov`."""
+    return estimate(state, t).cov
 
 
 def sample_unweighted_traces(state: ParticleFilterState, num_samples: int, seed: int = 0):

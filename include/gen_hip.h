@@ -14,6 +14,9 @@
  *   gh_pf_get_states /
  *   gh_pf_get_trajectory    get_traces (SoA columns)     src/inference/particle_filter.jl:31-34
  *   gh_pf_get_parents       ParticleFilterState.parents  src/inference/particle_filter.jl:23
+ *   gh_pf_estimate          effective_sample_size /      src/inference/particle_filter.jl:3-14, and
+ *                           normalize_weights            the expectation callers take over get_traces
+ *                                                        with get_log_weights
  *   gh_pf_get_scores        get_score / per-choice scores src/static_ir/trace.jl:91-129
  *   gh_pf_sample_unweighted sample_unweighted_traces     src/inference/particle_filter.jl:62-70
  *   gh_pf_rejuvenate        mh(trace, select(x_t)) on    src/inference/mh.jl:14-26 (applied per
@@ -404,6 +407,27 @@ int gh_pf_get_parents(gh_pf* pf, int64_t* host_out /* n_local, global ids */);
 /* latent of step t (1-based) of the current particles' traces: follows the
    genealogy back from the current step (record_history required) */
 int gh_pf_get_trajectory(gh_pf* pf, int t, double* host_out /* [d][n_local] */);
+/* The effective sample size and the weighted mean and covariance of the
+   current particles, reduced on the device: only the outputs asked for leave
+   it (at most 1 + d + d^2 doubles, one synchronise).  With w_i = exp(lw_i -
+   max lw), W = sum w_i and x_i the latent of step t of particle i's trace
+   (t = 0: the current step; 1 <= t <= the current step: along the genealogy,
+   as gh_pf_get_trajectory, record_history required for an earlier step):
+     ess      = W^2 / sum w_i^2
+     mean[k]  = sum w_i x_ik / W
+     cov[k][l] = sum w_i (x_ik - mean[k]) (x_il - mean[l]) / W
+   cov is the weighted POPULATION covariance (no Bessel correction), full,
+   row-major and exactly symmetric.  The estimate is of the stored doubles:
+   for a categorical latent it is the mean of the class index.  A particle of
+   weight exactly 0 adds nothing, whatever its state.  While a resample is
+   pending the particles are the resampled ones with equal weights (ess = n),
+   as gh_pf_get_states and gh_pf_get_log_weights report them.  Any of ess,
+   mean, cov may be NULL (all three NULL: GH_E_INVAL); ess alone runs no pass
+   over the particles, mean one, cov two (centred on the first pass's mean).
+   Log-weights all -inf, or holding a NaN: GH_E_NUMERIC.  One rank only: a
+   filter on the multi-rank path returns GH_E_STATE.  Every model family.
+   Deterministic: the same filter gives the same bits. */
+int gh_pf_estimate(gh_pf* pf, int t, double* ess /* 1 */, double* mean /* [d] */, double* cov /* [d][d] */);
 /* The score columns of the current particles' traces (the per-choice score
    fields of static_ir/trace.jl:91-129): total[i] = get_score(trace i), and
    (nullable) per_step[t-1][0][i] / per_step[t-1][1][i] = the scores of the
