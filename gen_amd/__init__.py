@@ -40,6 +40,8 @@ from .pf import (
     effective_sample_size,
     weighted_mean,
     weighted_covariance,
+    ParticleForecast,
+    forecast,
     gaussian_drift,
     GaussianDriftProposal,
     mh,
@@ -66,4 +68,5 @@ __all__ = [
     "metropolis_hastings", "mh", "simulate", "SimulatedTraces", "dists", "gaussian_drift", "GaussianDriftProposal",
     "choice_gradients", "mala", "hmc", "elliptical_slice", "map_optimize",
     "ParticleEstimate", "estimate", "effective_sample_size", "weighted_mean", "weighted_covariance",
+    "ParticleForecast", "forecast",
 ]

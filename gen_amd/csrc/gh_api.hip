@@ -31,6 +31,7 @@
 #include "gh_csmc.h"
 #include "gh_inst.h"
 #include "gh_moments.h"
+#include "gh_forecast.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
 
@@ -67,6 +68,13 @@ GH_SLICE_UNIT4(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT5(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT6(GH_EXTERN_TEMPLATE)
 GH_EST_UNIT(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT0(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT1(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT2(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT3(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT4(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT5(GH_EXTERN_TEMPLATE)
+GH_FC_UNIT6(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1357,6 +1365,13 @@ struct gh_pf {
   double* est_part = nullptr;
   const int32_t** est_ancs = nullptr;
   int est_ancs_cap = 0;
+  // gh_pf_forecast's scratch, allocated at its first use and grown with the
+  // horizon: the per-horizon result blocks, the block partials, the steps' constants
+  double* fc_res = nullptr;
+  double* fc_part = nullptr;
+  StepObs* fc_obs = nullptr;
+  int fc_cap = 0;                 // horizons fc_res and fc_obs hold
+  size_t fc_part_cap = 0;         // doubles of fc_part
   // kernel timing
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -1528,6 +1543,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->acc_count); hipFree(pf->exh_count); hipFree(pf->pin); hipFree(pf->amax);
   hipFree(pf->amax_all); hipFree(pf->rec); hipFree(pf->recs_all); hipFree(pf->qlin);
   hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs);
+  hipFree(pf->fc_res); hipFree(pf->fc_part); hipFree(pf->fc_obs);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
   if (pf->ev_plan) hipEventDestroy(pf->ev_plan);
@@ -3300,6 +3316,142 @@ extern "C" int gh_pf_estimate(gh_pf* pf, int t, double* ess, double* mean, doubl
   if (ess) *ess = h[0];
   if (mean) memcpy(mean, h + 1, sizeof(double) * D);
   if (cov) memcpy(cov, h + 1 + D, sizeof(double) * D * D);
+  return GH_OK;
+}
+
+// ------------------------------------------------ forecast on the device
+// The posterior predictive of x_{T+k} and y_{T+k}, k = 1..H (gh_forecast.h):
+// particle_filter_step! with no constraints on a copy of the state
+// (particle_filter.jl:139-160), without the copy — the filter is only read.
+template <int PASS>
+static int fc_pass(gh_pf* pf, FcArgs a, int H, unsigned nb, const FcPlan& pl) {
+  a.hc = pl.hc;
+  const gh_model* m = pf->m;
+  CHECK(with_model(m, [&](auto model, const auto& p) {
+    using M = decltype(model);
+    if constexpr (!std::is_same_v<M, RegModel>)  // (refused by the caller: no time extension)
+      hipLaunchKernelGGL((k_forecast<M, PASS>), dim3(nb, (unsigned)pl.chunks), dim3(64 * pl.nw), (size_t)pl.lds, pf->s,
+                         (const double*)m->dparams, p, a);
+  }));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_fc_fold, dim3((unsigned)H), dim3(1024), 0, pf->s, (const double*)pf->fc_part, (int)nb, pf->D,
+                     a.dy, PASS, a.e.stats, a.e.dev, a.e.live, pf->fc_res);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
+extern "C" int gh_pf_forecast(gh_pf* pf, int horizon, const double* inputs, double* x_mean, double* x_cov,
+                              double* y_mean, double* y_cov, double* xs, double* ys) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  if (!x_mean && !x_cov && !y_mean && !y_cov && !xs && !ys)
+    return set_err(GH_E_INVAL, "gh_pf_forecast: every output is null");
+  if (horizon < 1 || horizon > kFcMaxHorizon)
+    return set_err(GH_E_INVAL, "gh_pf_forecast: horizon %d outside 1..%d", horizon, kFcMaxHorizon);
+  const gh_model* m = pf->m;
+  const int T = pf->t, D = pf->D, H = horizon;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_forecast before init");
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "gh_pf_forecast: not for a filter sharded over ranks (the multi-rank path)");
+  if (m->family == GH_FAMILY_REGRESSION)
+    return set_err(GH_E_INVAL, "gh_pf_forecast: the regression model has no time steps");
+  if (D < 1 || D > 16) return set_err(GH_E_INVAL, "gh_pf_forecast: no kernel for a latent of %d components", D);
+  const bool takes = m->family == GH_FAMILY_SLOTS && m->slots.uoff >= 0;
+  if (takes && !inputs)
+    return set_err(GH_E_INVAL, "gh_pf_forecast: a slot model with per-step inputs takes them (inputs[horizon][d])");
+  if (!takes && inputs)
+    return set_err(GH_E_INVAL, "gh_pf_forecast: the model takes no per-step inputs (slot latent form 2)");
+  const int dy = (m->family == GH_FAMILY_LGSSM || m->family == GH_FAMILY_SLOTS) ? m->dy : 1;  // (simulate_impl's)
+  if (dy < 1 || dy > kMaxObs) return set_err(GH_E_INVAL, "gh_pf_forecast: %d observation components", dy);
+  if (pf->n < 1) return set_err(GH_E_STATE, "gh_pf_forecast: no particles");
+  std::vector<StepObs> hobs(H);  // (alive until the synchronise below)
+  for (int k = 1; k <= H; ++k) {
+    CHECK(make_obs(m, T + k, nullptr, &hobs[k - 1]));
+    if (inputs)
+      for (int j = 0; j < D; ++j) {
+        const double u = inputs[(size_t)(k - 1) * D + j];
+        if (!std::isfinite(u)) return set_err(GH_E_INVAL, "gh_pf_forecast: non-finite input");
+        hobs[k - 1].v[m->slots.uoff + j] = u;
+      }
+  }
+  const bool cov = x_cov || y_cov, samples = xs || ys;
+  const FcPlan pl0 = fc_plan(D, dy, 0, H), pl1 = fc_plan(D, dy, 1, H);
+  // the grid is a function of (n, H) and the model's sizes only
+  const int64_t tiles = (pf->n + kTileP - 1) / kTileP;
+  const unsigned nb0 = (unsigned)std::min<int64_t>((tiles + pl0.nw - 1) / pl0.nw, kFcMaxBlocks);
+  const unsigned nb1 = (unsigned)std::min<int64_t>((tiles + pl1.nw - 1) / pl1.nw, kFcMaxBlocks);
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  const int R = fc_result_doubles(D, dy);
+  if (pf->fc_cap < H) {
+    hipFree(pf->fc_res);
+    hipFree(pf->fc_obs);
+    pf->fc_res = nullptr;
+    pf->fc_obs = nullptr;
+    pf->fc_cap = 0;
+    HIP_TRY(hipMalloc(&pf->fc_res, sizeof(double) * (size_t)H * R));
+    HIP_TRY(hipMalloc(&pf->fc_obs, sizeof(StepObs) * (size_t)H));
+    pf->fc_cap = H;
+  }
+  const size_t need = std::max((size_t)H * fc_sums(D, dy, 0) * nb0, cov ? (size_t)H * fc_sums(D, dy, 1) * nb1 : 0);
+  if (pf->fc_part_cap < need) {
+    hipFree(pf->fc_part);
+    pf->fc_part = nullptr;
+    pf->fc_part_cap = 0;
+    HIP_TRY(hipMalloc(&pf->fc_part, sizeof(double) * need));
+    pf->fc_part_cap = need;
+  }
+  // the draws, when asked for: the only n x H memory, held for this call
+  const size_t nx = (size_t)H * D * pf->n, ny = (size_t)H * dy * pf->n;
+  double* samp = nullptr;
+  if (samples && hipMalloc(&samp, sizeof(double) * (nx + ny)) != hipSuccess)
+    return set_err(GH_E_NOMEM, "gh_pf_forecast: %d horizons x %lld draws", H, (long long)pf->n);
+  std::vector<double> h((size_t)H * R);
+  int rc = GH_OK;
+  do {
+    if ((rc = materialize_marks(pf)) || (rc = ensure_stats(pf))) break;
+    if (hipMemcpyAsync(pf->fc_obs, hobs.data(), sizeof(StepObs) * H, hipMemcpyHostToDevice, pf->s) != hipSuccess) {
+      rc = set_err(GH_E_HIP, "gh_pf_forecast: upload");
+      break;
+    }
+    FcArgs a{};
+    a.e.x = slot_x(pf, T);
+    a.e.anc_pending = pf->cap >= T + 1 ? anc_for_step(pf, T + 1) : nullptr;
+    a.e.logw = pf->logw;
+    a.e.stats = pf->stats_all;
+    a.e.dev = pf->dev;
+    a.e.n = pf->n;
+    a.e.t_target = a.e.t_cur = T;
+    a.e.live = flags_live(pf);
+    a.e.part = pf->fc_part;
+    a.obs = pf->fc_obs;
+    a.seed = pf->seed;
+    a.lo = pf->lo;
+    a.H = H;
+    a.dy = dy;
+    a.res = pf->fc_res;
+    a.sx = samp;
+    a.sy = samp ? samp + nx : nullptr;
+    if ((rc = fc_pass<0>(pf, a, H, nb0, pl0))) break;
+    if (cov && (rc = fc_pass<1>(pf, a, H, nb1, pl1))) break;
+    if ((xs && hipMemcpyAsync(xs, a.sx, sizeof(double) * nx, hipMemcpyDeviceToHost, pf->s) != hipSuccess) ||
+        (ys && hipMemcpyAsync(ys, a.sy, sizeof(double) * ny, hipMemcpyDeviceToHost, pf->s) != hipSuccess)) {
+      rc = set_err(GH_E_HIP, "gh_pf_forecast: download");
+      break;
+    }
+    rc = d2h(pf, h.data(), pf->fc_res, sizeof(double) * h.size());
+  } while (0);
+  if (samp) {
+    if (rc) hipStreamSynchronize(pf->s);  // (nothing of this call still writes the buffer)
+    hipFree(samp);
+  }
+  if (rc) return rc;
+  if (!(h[0] > 0.0 && h[0] < INFINITY))  // W: the sum of exp(lw - max)
+    return set_err(GH_E_NUMERIC, "gh_pf_forecast: the log-weights are all -inf, or hold a NaN or +inf");
+  for (int k = 0; k < H; ++k) {
+    const double* r = h.data() + (size_t)k * R;
+    if (x_mean) memcpy(x_mean + (size_t)k * D, r + 1, sizeof(double) * D);
+    if (y_mean) memcpy(y_mean + (size_t)k * dy, r + 1 + D, sizeof(double) * dy);
+    if (x_cov) memcpy(x_cov + (size_t)k * D * D, r + 1 + D + dy, sizeof(double) * D * D);
+    if (y_cov) memcpy(y_cov + (size_t)k * dy * dy, r + 1 + D + dy + D * D, sizeof(double) * dy * dy);
+  }
   return GH_OK;
 }
 

@@ -1,0 +1,5 @@
+// gh_inst_forecast4.hip — explicit instantiations of the forecast kernels (gh_forecast.h; see gh_inst.h)
+#include <hip/hip_runtime.h>
+#include "gh_forecast.h"
+
+GH_FC_UNIT4(template)

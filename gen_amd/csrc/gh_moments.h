@@ -91,15 +91,18 @@ __device__ __forceinline__ void est_lds_order() {
 // (5 KiB of LDS private to the wave; lane l's row starts 20 banks after lane
 // l-1's, so the 16-lane groups of a 16-byte read meet no conflict).  The
 // gather paths index by xidx along the genealogy, as k_traj does.
+// nw: the block's waves (k_forecast launches fewer than kBlock / 64 when its
+// LDS asks for it); an f that takes a third argument gets the lane's particle
+// index, which is past n in the last tile's tail (weight 0, state unspecified).
 template <int D, class F>
-__device__ __forceinline__ void est_tiles(const EstArgs& a, est_d2* stage, F&& f) {
+__device__ __forceinline__ void est_tiles(const EstArgs& a, est_d2* stage, F&& f, const int nw = kBlock / 64) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bool uniform = a.live && (a.dev->pending | a.dev->fire);
   const bool walk = a.t_target != a.t_cur;
   const bool gather = walk || (uniform && a.anc_pending);
   const double M = a.stats[0];
   const int64_t tiles = (a.n + kTileP - 1) / kTileP;
-  for (int64_t tile = (int64_t)blockIdx.x * (kBlock / 64) + w; tile < tiles; tile += (int64_t)gridDim.x * (kBlock / 64)) {
+  for (int64_t tile = (int64_t)blockIdx.x * nw + w; tile < tiles; tile += (int64_t)gridDim.x * nw) {
     const int64_t j = tile * kTileP + lane;
     const bool in = j < a.n;
     double wt = 0.0;
@@ -147,7 +150,10 @@ __device__ __forceinline__ void est_tiles(const EstArgs& a, est_d2* stage, F&& f
       }
       if constexpr ((D & 1) != 0) x[D - 1] = tb[(D - 1) * kTileP + lane];
     }
-    f(wt, x);
+    if constexpr (std::is_invocable_v<F&, double, const double*, int64_t>)
+      f(wt, x, j);
+    else
+      f(wt, x);
   }
 }
 

@@ -714,6 +714,53 @@ def weighted_covariance(state: ParticleFilterState, t: int | None = None) -> np.
     return estimate(state, t).cov
 
 
+class ParticleForecast(NamedTuple):
+    """`forecast`'s result, horizon k at index k-1: the weighted mean [H, d]
+    and population covariance [H, d, d] of x_{T+k}, the same of y_{T+k}
+    ([H, dy], [H, dy, dy]), and the draws xs [H, n_local, d], ys [H, n_local,
+    dy] (the covariances and the draws None when not asked for)."""
+    x_mean: np.ndarray
+    x_cov: np.ndarray | None
+    y_mean: np.ndarray
+    y_cov: np.ndarray | None
+    xs: np.ndarray | None
+    ys: np.ndarray | None
+
+
+def forecast(state: ParticleFilterState, horizon: int, inputs=None, cov: bool = True,
+             samples: bool = False) -> ParticleForecast:
+    """The posterior predictive of x_{T+k} and y_{T+k}, k = 1..horizon, given
+    the data up to the current step T (gh_pf_forecast): what
+    particle_filter_step!(copy, (T+k,), (UnknownChange(),), EmptyChoiceMap())
+    (particle_filter.jl:139-160) on a copy of the state would hold, with :y
+    drawn as simulate draws it — without the copy: the filter is only read and
+    continues bit for bit.  Each particle is advanced by the model's own
+    transition with the draws an unobserved default-proposal step would use,
+    so xs[k-1] is bit for bit states() after k such steps without a resample,
+    under unchanged weights; the moments are `estimate`'s (weighted mean,
+    population covariance, the particles and weights of a pending resample).
+    inputs: [horizon, d], row k-1 the input u_{T+k}, for a slot model with
+    per-step inputs.  cov=False skips the second propagation; samples=True is
+    the only mode that uses memory of n x horizon.  horizon in 1..64.  One
+    rank only; not for the regression model."""
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or not 1 <= int(horizon) <= 64:
+        raise _lib.GenHipError(1, f"horizon {horizon!r} outside 1..64")
+    H, m, n = int(horizon), state.model, state.n_local
+    vec = m.family in (_lib.FAMILY_LGSSM, _lib.FAMILY_REGRESSION, _lib.FAMILY_SLOTS)
+    d, dy = (m.d, m.dy) if vec else (1, 1)
+    U = None
+    if inputs is not None:
+        U = np.ascontiguousarray(np.asarray(inputs, dtype=np.float64).reshape(H, d))
+    x_mean, y_mean = np.empty((H, d)), np.empty((H, dy))
+    x_cov, y_cov = (np.empty((H, d, d)), np.empty((H, dy, dy))) if cov else (None, None)
+    xs, ys = (np.empty((H, d, n)), np.empty((H, dy, n))) if samples else (None, None)
+    _lib.check(_lib.load().gh_pf_forecast(state.h, H, _lib.dptr(U), _lib.dptr(x_mean), _lib.dptr(x_cov),
+                                          _lib.dptr(y_mean), _lib.dptr(y_cov), _lib.dptr(xs), _lib.dptr(ys)))
+    if samples:
+        xs, ys = np.ascontiguousarray(xs.transpose(0, 2, 1)), np.ascontiguousarray(ys.transpose(0, 2, 1))
+    return ParticleForecast(x_mean, x_cov, y_mean, y_cov, xs, ys)
+
+
 def sample_unweighted_traces(state: ParticleFilterState, num_samples: int, seed: int = 0):
     """Indices (and views) of num_samples traces drawn ∝ normalised weights."""
     idx = np.empty(int(num_samples), dtype=np.int64)

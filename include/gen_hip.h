@@ -17,6 +17,11 @@
  *   gh_pf_estimate          effective_sample_size /      src/inference/particle_filter.jl:3-14, and
  *                           normalize_weights            the expectation callers take over get_traces
  *                                                        with get_log_weights
+ *   gh_pf_forecast          particle_filter_step! with   src/inference/particle_filter.jl:139-160 on a
+ *                           EmptyChoiceMap() on a copy   copy of the state; the Unfold extended by
+ *                           of the state, k = 1..H, and  update with no constraints
+ *                           :y drawn as simulate does    (src/modeling_library/unfold/update.jl:54-78);
+ *                                                        :y as src/static_ir/simulate.jl:23-34
  *   gh_pf_get_scores        get_score / per-choice scores src/static_ir/trace.jl:91-129
  *   gh_pf_sample_unweighted sample_unweighted_traces     src/inference/particle_filter.jl:62-70
  *   gh_pf_rejuvenate        mh(trace, select(x_t)) on    src/inference/mh.jl:14-26 (applied per
@@ -428,6 +433,36 @@ int gh_pf_get_trajectory(gh_pf* pf, int t, double* host_out /* [d][n_local] */);
    filter on the multi-rank path returns GH_E_STATE.  Every model family.
    Deterministic: the same filter gives the same bits. */
 int gh_pf_estimate(gh_pf* pf, int t, double* ess /* 1 */, double* mean /* [d] */, double* cov /* [d][d] */);
+/* The posterior predictive of x_{T+k} and y_{T+k}, k = 1..horizon, given the
+   data up to the current step T, reduced on the device; the filter is only
+   read (t, states, weights, log-ML, history, a pending resample and the move
+   counters stay as they are, and it continues bit for bit as a filter that
+   made no forecast).  Particle i's latent is advanced by the model's own
+   transition with exactly the draws an unobserved default-proposal
+   gh_pf_step would use (a custom proposal of the filter is not applied), so
+   xs[k-1] holds bit for bit what the filter's states would be after k
+   unobserved steps without a resample, under unchanged weights; y_{T+k} is
+   drawn from x_{T+k} with gh_simulate's observation noise, keyed by (seed,
+   particle, T+k).  Particles and weights are gh_pf_estimate's: the resampled
+   particles with equal weights while a resample is pending; a particle of
+   weight exactly 0 adds nothing; log-weights all -inf, or holding a NaN or
+   +inf: GH_E_NUMERIC.  Per horizon k: the weighted mean and the weighted
+   POPULATION covariance (gh_pf_estimate's definitions and two-pass centring,
+   exactly symmetric) of x and of y, and optionally the draws themselves in
+   gh_simulate's layout.  dy: the model's dy for the LG-SSM and slot models, 1
+   for the HMM (the symbol) and Kitagawa.  inputs: [horizon][d], row k-1 the
+   input u_{T+k} of a slot model with per-step inputs (latent form 2), which is
+   refused without them as every other model is with them; finite values
+   only.  Every output may be NULL (all NULL: GH_E_INVAL); the covariances
+   cost a second propagation, the draws the only memory of n x horizon.
+   horizon is 1..64, an interface limit that bounds the block-partials buffer.
+   One rank only (GH_E_STATE on the multi-rank path); not for the regression
+   family, which has no time extension (GH_E_INVAL).  One synchronise.
+   Deterministic: the same filter gives the same bits. */
+int gh_pf_forecast(gh_pf* pf, int horizon, const double* inputs /* [horizon][d] or NULL */,
+                   double* x_mean /* [H][d] */, double* x_cov /* [H][d][d] */,
+                   double* y_mean /* [H][dy] */, double* y_cov /* [H][dy][dy] */,
+                   double* xs /* [H][d][n_local] */, double* ys /* [H][dy][n_local] */);
 /* The score columns of the current particles' traces (the per-choice score
    fields of static_ir/trace.jl:91-129): total[i] = get_score(trace i), and
    (nullable) per_step[t-1][0][i] / per_step[t-1][1][i] = the scores of the
