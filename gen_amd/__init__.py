@@ -40,6 +40,9 @@ from .pf import (
     effective_sample_size,
     weighted_mean,
     weighted_covariance,
+    quantiles,
+    weighted_median,
+    credible_interval,
     ParticleForecast,
     forecast,
     gaussian_drift,
@@ -68,5 +71,6 @@ __all__ = [
     "metropolis_hastings", "mh", "simulate", "SimulatedTraces", "dists", "gaussian_drift", "GaussianDriftProposal",
     "choice_gradients", "mala", "hmc", "elliptical_slice", "map_optimize",
     "ParticleEstimate", "estimate", "effective_sample_size", "weighted_mean", "weighted_covariance",
+    "quantiles", "weighted_median", "credible_interval",
     "ParticleForecast", "forecast",
 ]

@@ -31,6 +31,7 @@
 #include "gh_csmc.h"
 #include "gh_inst.h"
 #include "gh_moments.h"
+#include "gh_quantiles.h"
 #include "gh_forecast.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
@@ -68,6 +69,7 @@ GH_SLICE_UNIT4(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT5(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT6(GH_EXTERN_TEMPLATE)
 GH_EST_UNIT(GH_EXTERN_TEMPLATE)
+GH_QT_UNIT(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT0(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT1(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT2(GH_EXTERN_TEMPLATE)
@@ -1365,6 +1367,9 @@ struct gh_pf {
   double* est_part = nullptr;
   const int32_t** est_ancs = nullptr;
   int est_ancs_cap = 0;
+  // gh_pf_quantiles' scratch, allocated at its first use: the histogram, the
+  // pairs' prefixes and ranks, the control words, the result block (gh_quantiles.h)
+  uint64_t* qt_buf = nullptr;
   // gh_pf_forecast's scratch, allocated at its first use and grown with the
   // horizon: the per-horizon result blocks, the block partials, the steps' constants
   double* fc_res = nullptr;
@@ -1542,7 +1547,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->mn_key); hipFree(pf->mn_pos); hipFree(pf->mn_anc); hipFree(pf->mn_bcnt); hipFree(pf->mn_boff);
   hipFree(pf->acc_count); hipFree(pf->exh_count); hipFree(pf->pin); hipFree(pf->amax);
   hipFree(pf->amax_all); hipFree(pf->rec); hipFree(pf->recs_all); hipFree(pf->qlin);
-  hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs);
+  hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs); hipFree(pf->qt_buf);
   hipFree(pf->fc_res); hipFree(pf->fc_part); hipFree(pf->fc_obs);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
@@ -3251,6 +3256,24 @@ static int est_pass(gh_pf* pf, const EstArgs& a, unsigned nb, bool cov) {
   return GH_OK;
 }
 
+// the per-step ancestor arrays of a walk to an earlier step, on the device at
+// pf->est_ancs (ha: the host copy, to be kept alive until the stream is synchronised)
+static int est_stage_ancs(gh_pf* pf, std::vector<const int32_t*>& ha) {
+  const int T = pf->t;
+  if (pf->est_ancs_cap < T) {
+    hipFree(pf->est_ancs);
+    pf->est_ancs = nullptr;
+    pf->est_ancs_cap = 0;
+    const int nc = std::max(pf->cap, T);
+    HIP_TRY(hipMalloc(&pf->est_ancs, sizeof(int32_t*) * (size_t)nc));
+    pf->est_ancs_cap = nc;
+  }
+  ha.resize(T);
+  for (int s = 1; s <= T; ++s) ha[s - 1] = anc_for_step(pf, s);
+  HIP_TRY(hipMemcpyAsync(pf->est_ancs, ha.data(), sizeof(int32_t*) * T, hipMemcpyHostToDevice, pf->s));
+  return GH_OK;
+}
+
 extern "C" int gh_pf_estimate(gh_pf* pf, int t, double* ess, double* mean, double* cov) {
   if (!pf) return set_err(GH_E_INVAL, "null pf");
   if (!ess && !mean && !cov) return set_err(GH_E_INVAL, "gh_pf_estimate: ess, mean and cov are all null");
@@ -3272,19 +3295,7 @@ extern "C" int gh_pf_estimate(gh_pf* pf, int t, double* ess, double* mean, doubl
   if (states && !pf->est_part)
     HIP_TRY(hipMalloc(&pf->est_part, sizeof(double) * (size_t)est_entries(D) * nb));
   std::vector<const int32_t*> ha;  // (alive until the synchronise below)
-  if (states && t != T) {
-    if (pf->est_ancs_cap < T) {
-      hipFree(pf->est_ancs);
-      pf->est_ancs = nullptr;
-      pf->est_ancs_cap = 0;
-      const int nc = std::max(pf->cap, T);
-      HIP_TRY(hipMalloc(&pf->est_ancs, sizeof(int32_t*) * (size_t)nc));
-      pf->est_ancs_cap = nc;
-    }
-    ha.resize(T);
-    for (int s = 1; s <= T; ++s) ha[s - 1] = anc_for_step(pf, s);
-    HIP_TRY(hipMemcpyAsync(pf->est_ancs, ha.data(), sizeof(int32_t*) * T, hipMemcpyHostToDevice, pf->s));
-  }
+  if (states && t != T) CHECK(est_stage_ancs(pf, ha));
   if (states) CHECK(materialize_marks(pf));
   CHECK(ensure_stats(pf));
   hipLaunchKernelGGL(k_est_ess, dim3(1), dim3(64), 0, pf->s, (const double*)pf->stats_all,
@@ -3316,6 +3327,98 @@ extern "C" int gh_pf_estimate(gh_pf* pf, int t, double* ess, double* mean, doubl
   if (ess) *ess = h[0];
   if (mean) memcpy(mean, h + 1, sizeof(double) * D);
   if (cov) memcpy(cov, h + 1 + D, sizeof(double) * D * D);
+  return GH_OK;
+}
+
+// ------------------------------------------------ quantiles on the device
+// The median and the credible band a caller would take from get_traces with
+// get_log_weights by a sort per component, selected where the particles are
+// (gh_quantiles.h): n_probs x d doubles leave the device, after one stream
+// synchronise.  Plain launches in stream order: per pass the histogram over
+// the particles, then the one-block select.
+template <int D>
+static void launch_qt_hist(gh_pf* pf, const QtArgs& a, unsigned nb) {
+  const unsigned chunks = (unsigned)((a.n_probs + qt_chunk_probs(D) - 1) / qt_chunk_probs(D));
+  hipLaunchKernelGGL(k_qt_hist<D>, dim3(nb, chunks), dim3(kBlock), 0, pf->s, a);
+}
+
+extern "C" int gh_pf_quantiles(gh_pf* pf, int t, int n_probs, const double* probs, double* out) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  const int T = pf->t, D = pf->D;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_quantiles before init");
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "gh_pf_quantiles: not for a filter sharded over ranks (the multi-rank path)");
+  if (t < 0 || t > T) return set_err(GH_E_INVAL, "step %d outside 1..%d", t, T);
+  if (t == 0) t = T;
+  if (!pf->opts.record_history && t != T)
+    return set_err(GH_E_STATE, "record_history is off: only the current step is kept");
+  if (D < 1 || D > 16) return set_err(GH_E_INVAL, "gh_pf_quantiles: no kernel for a latent of %d components", D);
+  if (n_probs < 1 || n_probs > kQtMaxProbs)
+    return set_err(GH_E_INVAL, "gh_pf_quantiles: %d probabilities outside 1..%d", n_probs, kQtMaxProbs);
+  if (!probs || !out) return set_err(GH_E_INVAL, "gh_pf_quantiles: null probs or out");
+  QtSel sel{};
+  for (int j = 0; j < n_probs; ++j) {
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
+      return set_err(GH_E_INVAL, "gh_pf_quantiles: probability %d (%g) outside [0, 1]", j, probs[j]);
+    sel.u[j] = (uint64_t)(probs[j] * 0x1p53);  // exact: a scaling by a power of two, then the floor
+  }
+  if (pf->n < 1) return set_err(GH_E_STATE, "gh_pf_quantiles: no particles");
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  // the grid is a function of n only (gh_pf_estimate's), times the chunks of n_probs
+  const int64_t tiles = (pf->n + kTileP - 1) / kTileP;
+  const unsigned nb = (unsigned)std::min<int64_t>((tiles + kBlock / 64 - 1) / (kBlock / 64), kEstMaxBlocks);
+  if (!pf->qt_buf) HIP_TRY(hipMalloc(&pf->qt_buf, sizeof(uint64_t) * kQtScratchWords));
+  const int pairs = n_probs * D;
+  sel.hist = pf->qt_buf;
+  sel.prefix = pf->qt_buf + kQtHistWords;
+  sel.rank = sel.prefix + kQtMaxPairs;
+  sel.ctl = sel.rank + kQtMaxPairs;
+  sel.res = (double*)(sel.ctl + kQtCtlWords);
+  sel.pairs = pairs;
+  sel.D = D;
+  std::vector<const int32_t*> ha;  // (alive until the synchronise below)
+  if (t != T) CHECK(est_stage_ancs(pf, ha));
+  CHECK(materialize_marks(pf));
+  CHECK(ensure_stats(pf));
+  HIP_TRY(hipMemsetAsync(sel.hist, 0, sizeof(uint64_t) * (size_t)pairs * kQtBins, pf->s));
+  // the marker: res[0] = the ESS, NaN for unusable log-weights (k_qt_select adds S = 0)
+  hipLaunchKernelGGL(k_est_ess, dim3(1), dim3(64), 0, pf->s, (const double*)pf->stats_all,
+                     (const DevScalars*)pf->dev, flags_live(pf), pf->n, sel.res);
+  HIP_TRY(hipGetLastError());
+  QtArgs a{};
+  a.e.x = slot_x(pf, t);
+  a.e.ancs = pf->est_ancs;
+  a.e.res_before = pf->res_hist;
+  a.e.anc_pending = pf->cap >= T + 1 ? anc_for_step(pf, T + 1) : nullptr;
+  a.e.logw = pf->logw;
+  a.e.stats = pf->stats_all;
+  a.e.dev = pf->dev;
+  a.e.n = pf->n;
+  a.e.t_target = t;
+  a.e.t_cur = T;
+  a.e.live = flags_live(pf);
+  a.hist = sel.hist;
+  a.prefix = sel.prefix;
+  a.ctl = sel.ctl;
+  a.qscale = as_f64((uint64_t)(quant_shift((uint64_t)pf->n) + 1023) << 52);
+  a.n_probs = n_probs;
+  for (int pass = 0; pass < kQtPasses; ++pass) {
+    a.pass = sel.pass = pass;
+    switch (D) {
+#define GH_QT_CASE(D) case D: launch_qt_hist<D>(pf, a, nb); break;
+      GH_QT_CASE(1) GH_QT_CASE(2) GH_QT_CASE(3) GH_QT_CASE(4) GH_QT_CASE(5) GH_QT_CASE(6) GH_QT_CASE(7) GH_QT_CASE(8)
+      GH_QT_CASE(9) GH_QT_CASE(10) GH_QT_CASE(11) GH_QT_CASE(12) GH_QT_CASE(13) GH_QT_CASE(14) GH_QT_CASE(15)
+      GH_QT_CASE(16)
+#undef GH_QT_CASE
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_qt_select, dim3(1), dim3(1024), 0, pf->s, sel);
+    HIP_TRY(hipGetLastError());
+  }
+  double h[1 + kQtMaxPairs];
+  CHECK(d2h(pf, h, sel.res, sizeof(double) * (1 + pairs)));
+  if (h[0] != h[0])
+    return set_err(GH_E_NUMERIC, "gh_pf_quantiles: the log-weights are all -inf, or hold a NaN or +inf");
+  memcpy(out, h + 1, sizeof(double) * pairs);
   return GH_OK;
 }
 

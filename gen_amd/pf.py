@@ -714,6 +714,54 @@ def weighted_covariance(state: ParticleFilterState, t: int | None = None) -> np.
     return estimate(state, t).cov
 
 
+def quantiles(state: ParticleFilterState, probs, t: int | None = None) -> np.ndarray:
+    """Weighted quantiles of the filtered posterior, per component, selected on
+    the device (gh_pf_quantiles): row j holds Q_k(probs[j]) for the d
+    components of the latent of step t (default: current) along the particles'
+    genealogy; shape [len(probs), d].  The median and the credible band a
+    caller would take by a sort per component over get_traces with
+    get_log_weights, without copying either to the host.
+
+    The definition is on the resampler's integer weights, so it is exact and
+    the same bits on every run: q_i = floor(exp(lw_i - max lw) 2^shift), shift
+    = 62 - ceil(log2 n) (at most 52), every q_i = 2^shift while a resample is
+    pending (`estimate`'s particles and weights); S = sum q_i; for p in [0, 1],
+    u = floor(p 2^53) and the rank r = max(1, ceil(u S / 2^53)) in integer
+    arithmetic.  Q_k(p) is the smallest x_ik among the particles with q_i > 0
+    whose cumulative weight sum_{x_lk <= x_ik} q_l reaches r: the inverse CDF
+    (type 1), p = 0 the minimum of the support, p = 1 the maximum, always the
+    value of a particle that carries weight (for a categorical latent a class
+    index).  Doubles are ordered by their total order: -0.0 < +0.0.
+    probs: 1..16 floats in [0, 1].  The filter is only read.  One rank only."""
+    step = _estimate_step(state, t)
+    try:
+        p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError) as e:
+        raise _lib.GenHipError(1, f"probs {probs!r}: not a sequence of floats") from e
+    if not 1 <= p.size <= 16:
+        raise _lib.GenHipError(1, f"{p.size} probabilities outside 1..16")
+    if not ((p >= 0.0) & (p <= 1.0)).all():
+        raise _lib.GenHipError(1, f"probabilities {probs!r} outside [0, 1]")
+    out = np.empty((p.size, state.model.d), dtype=np.float64)
+    _lib.check(_lib.load().gh_pf_quantiles(state.h, step, int(p.size), _lib.dptr(p), _lib.dptr(out)))
+    return out
+
+
+def weighted_median(state: ParticleFilterState, t: int | None = None) -> np.ndarray:
+    """`quantiles(state, [0.5], t)[0]`."""
+    return quantiles(state, [0.5], t)[0]
+
+
+def credible_interval(state: ParticleFilterState, level: float = 0.9, t: int | None = None):
+    """The equal-tailed credible interval (lo, hi) at `level` in (0, 1]: the
+    rows of `quantiles(state, [(1 - level) / 2, (1 + level) / 2], t)`."""
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.floating)) or not 0.0 < float(level) <= 1.0:
+        raise _lib.GenHipError(1, f"level {level!r} outside (0, 1]")
+    level = float(level)
+    q = quantiles(state, [(1.0 - level) / 2.0, (1.0 + level) / 2.0], t)
+    return q[0], q[1]
+
+
 class ParticleForecast(NamedTuple):
     """`forecast`'s result, horizon k at index k-1: the weighted mean [H, d]
     and population covariance [H, d, d] of x_{T+k}, the same of y_{T+k}

@@ -17,6 +17,9 @@
  *   gh_pf_estimate          effective_sample_size /      src/inference/particle_filter.jl:3-14, and
  *                           normalize_weights            the expectation callers take over get_traces
  *                                                        with get_log_weights
+ *   gh_pf_quantiles         the weighted median and      src/inference/particle_filter.jl:31-45: the sort
+ *                           credible band of get_traces  per component callers run over get_traces with
+ *                           under get_log_weights        get_log_weights (normalize_weights, :8-14)
  *   gh_pf_forecast          particle_filter_step! with   src/inference/particle_filter.jl:139-160 on a
  *                           EmptyChoiceMap() on a copy   copy of the state; the Unfold extended by
  *                           of the state, k = 1..H, and  update with no constraints
@@ -433,6 +436,38 @@ int gh_pf_get_trajectory(gh_pf* pf, int t, double* host_out /* [d][n_local] */);
    filter on the multi-rank path returns GH_E_STATE.  Every model family.
    Deterministic: the same filter gives the same bits. */
 int gh_pf_estimate(gh_pf* pf, int t, double* ess /* 1 */, double* mean /* [d] */, double* cov /* [d][d] */);
+/* Weighted quantiles of the current particles, per component, selected on the
+   device: out[j][k] = Q_k(probs[j]); n_probs x d doubles leave it, after one
+   synchronise.  The definition is on the resampler's integer weights, so it
+   is exact and the same bits on every run.  With n the particle count, x_i
+   the latent of step t along particle i's genealogy (gh_pf_estimate's meaning
+   of t, 0 = the current step), lw_i its log-weight and M = max lw:
+     shift = 62 - ceil(log2 n), at most 52          (the resampler's)
+     q_i   = floor(exp(lw_i - M) 2^shift)           an unsigned integer; lw_i = -inf: 0
+     S     = sum q_i
+   and for a probability p in [0, 1]
+     u     = floor(p 2^53)                          exact in fp64
+     r     = max(1, ceil(u S / 2^53))               exact integer arithmetic; p = 1: r = S
+   While a resample is pending the particles are the resampled ones and every
+   q_i = 2^shift: the particles and weights gh_pf_estimate uses.  Doubles are
+   ordered by the total-order key, the bit pattern with all bits flipped for
+   negatives and the sign bit flipped otherwise: -0.0 < +0.0, and a NaN state
+   sorts by its bits and is not refused.  Then
+     Q_k(p) = the smallest v among {x_ik : q_i > 0} with sum_{i : x_ik <= v} q_i >= r,
+   returned with the bits of the particle that holds it: the inverse CDF
+   (type 1).  p = 0 gives the minimum of the support, p = 1 the maximum; the
+   result is always the value of a particle with q_i > 0, so for a categorical
+   latent it is a class index.  n_probs is 1..16, an interface limit that
+   bounds the scratch; n_probs outside it, a NULL probs or out, or a
+   probability that is NaN or outside [0, 1]: GH_E_INVAL, before any device
+   work.  Otherwise refused as gh_pf_estimate: before init and on the
+   multi-rank path GH_E_STATE, t outside 0..T GH_E_INVAL, an earlier step
+   without record_history GH_E_STATE, log-weights all -inf (S = 0) or holding
+   a NaN or +inf GH_E_NUMERIC.  The filter is only read (t, states, weights,
+   log-ML, history, a pending resample and the move counters stay as they are)
+   and continues bit for bit.  Every model family. */
+int gh_pf_quantiles(gh_pf* pf, int t, int n_probs, const double* probs /* [n_probs] */,
+                    double* out /* [n_probs][d] */);
 /* The posterior predictive of x_{T+k} and y_{T+k}, k = 1..horizon, given the
    data up to the current step T, reduced on the device; the filter is only
    read (t, states, weights, log-ML, history, a pending resample and the move
