@@ -43,6 +43,11 @@ from .pf import (
     quantiles,
     weighted_median,
     credible_interval,
+    ParticlePathEstimate,
+    estimate_path,
+    quantiles_path,
+    median_path,
+    credible_band,
     ParticleForecast,
     forecast,
     gaussian_drift,
@@ -72,5 +77,6 @@ __all__ = [
     "choice_gradients", "mala", "hmc", "elliptical_slice", "map_optimize",
     "ParticleEstimate", "estimate", "effective_sample_size", "weighted_mean", "weighted_covariance",
     "quantiles", "weighted_median", "credible_interval",
+    "ParticlePathEstimate", "estimate_path", "quantiles_path", "median_path", "credible_band",
     "ParticleForecast", "forecast",
 ]

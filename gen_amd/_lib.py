@@ -103,6 +103,9 @@ SIGNATURES = {
     "gh_pf_get_trajectory": (c_int, [c_void_p, c_int, POINTER(c_double)]),
     "gh_pf_estimate": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "gh_pf_quantiles": (c_int, [c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    "gh_pf_estimate_path": (c_int, [c_void_p, c_int, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double),
+                                    POINTER(c_double)]),
+    "gh_pf_quantiles_path": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     "gh_pf_forecast": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double),
                                POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "gh_pf_sample_unweighted": (c_int, [c_void_p, c_int64, c_uint64, POINTER(c_int64)]),

@@ -32,6 +32,7 @@
 #include "gh_inst.h"
 #include "gh_moments.h"
 #include "gh_quantiles.h"
+#include "gh_path.h"
 #include "gh_forecast.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
@@ -70,6 +71,7 @@ GH_SLICE_UNIT5(GH_EXTERN_TEMPLATE)
 GH_SLICE_UNIT6(GH_EXTERN_TEMPLATE)
 GH_EST_UNIT(GH_EXTERN_TEMPLATE)
 GH_QT_UNIT(GH_EXTERN_TEMPLATE)
+GH_PATH_UNIT(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT0(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT1(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT2(GH_EXTERN_TEMPLATE)
@@ -1370,6 +1372,14 @@ struct gh_pf {
   // gh_pf_quantiles' scratch, allocated at its first use: the histogram, the
   // pairs' prefixes and ranks, the control words, the result block (gh_quantiles.h)
   uint64_t* qt_buf = nullptr;
+  // gh_pf_estimate_path's and gh_pf_quantiles_path's scratch, allocated at
+  // their first use: the cursor and the ancestors' integer weights ([n] each),
+  // k_path_diag's block partials, the steps' result blocks (grown with the range)
+  int32_t* path_cur = nullptr;
+  unsigned long long* path_m = nullptr;
+  uint64_t* path_part = nullptr;
+  double* path_res = nullptr;
+  size_t path_res_cap = 0;        // doubles of path_res
   // gh_pf_forecast's scratch, allocated at its first use and grown with the
   // horizon: the per-horizon result blocks, the block partials, the steps' constants
   double* fc_res = nullptr;
@@ -1548,6 +1558,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->acc_count); hipFree(pf->exh_count); hipFree(pf->pin); hipFree(pf->amax);
   hipFree(pf->amax_all); hipFree(pf->rec); hipFree(pf->recs_all); hipFree(pf->qlin);
   hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs); hipFree(pf->qt_buf);
+  hipFree(pf->path_cur); hipFree(pf->path_m); hipFree(pf->path_part); hipFree(pf->path_res);
   hipFree(pf->fc_res); hipFree(pf->fc_part); hipFree(pf->fc_obs);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
@@ -3419,6 +3430,234 @@ extern "C" int gh_pf_quantiles(gh_pf* pf, int t, int n_probs, const double* prob
   if (h[0] != h[0])
     return set_err(GH_E_NUMERIC, "gh_pf_quantiles: the log-weights are all -inf, or hold a NaN or +inf");
   memcpy(out, h + 1, sizeof(double) * pairs);
+  return GH_OK;
+}
+
+// ------------------------------------------------ every step's summary in one walk
+// gh_pf_estimate and gh_pf_quantiles for t = t0..t1 (gh_path.h): one backward
+// sweep over a cursor instead of a walk from T inside every pass of every
+// call.  Plain launches in stream order, no synchronise inside the sweep, one
+// copy of the steps' result blocks at its end.
+struct PathSweep {
+  int t0, t1, L;
+  unsigned nb;  // the grid of the per-step calls (a function of n only)
+  std::vector<const int32_t*> ha;  // (alive until the synchronise)
+};
+
+// the refusals the two entry points share, then the scratch and what the sweep reads
+static int path_open(gh_pf* pf, const char* fn, int t0, int t1, size_t res_doubles_per_step, PathSweep& sw) {
+  const int T = pf->t, D = pf->D;
+  if (T < 1) return set_err(GH_E_STATE, "%s before init", fn);
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "%s: not for a filter sharded over ranks (the multi-rank path)", fn);
+  if (t1 == 0) t1 = T;
+  if (t0 < 1 || t1 > T || t1 < 0 || t0 > t1)
+    return set_err(GH_E_INVAL, "%s: steps %d..%d outside 1..%d or empty", fn, t0, t1, T);
+  if (!pf->opts.record_history && t0 != T)
+    return set_err(GH_E_STATE, "record_history is off: only the current step is kept");
+  if (D < 1 || D > 16) return set_err(GH_E_INVAL, "%s: no kernel for a latent of %d components", fn, D);
+  if (pf->n < 1) return set_err(GH_E_STATE, "%s: no particles", fn);
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  sw.t0 = t0;
+  sw.t1 = t1;
+  sw.L = t1 - t0 + 1;
+  const int64_t tiles = (pf->n + kTileP - 1) / kTileP;
+  sw.nb = (unsigned)std::min<int64_t>((tiles + kBlock / 64 - 1) / (kBlock / 64), kEstMaxBlocks);
+  if (!pf->path_cur) HIP_TRY(hipMalloc(&pf->path_cur, sizeof(int32_t) * (size_t)pf->n));
+  const size_t need = 1 + res_doubles_per_step * (size_t)sw.L;  // the marker, then the steps' blocks
+  if (pf->path_res_cap < need) {
+    hipFree(pf->path_res);
+    pf->path_res = nullptr;
+    pf->path_res_cap = 0;
+    HIP_TRY(hipMalloc(&pf->path_res, sizeof(double) * need));
+    pf->path_res_cap = need;
+  }
+  if (t0 != T) CHECK(est_stage_ancs(pf, sw.ha));
+  CHECK(materialize_marks(pf));
+  CHECK(ensure_stats(pf));
+  // the marker: the ESS, NaN for unusable log-weights
+  hipLaunchKernelGGL(k_est_ess, dim3(1), dim3(64), 0, pf->s, (const double*)pf->stats_all,
+                     (const DevScalars*)pf->dev, flags_live(pf), pf->n, pf->path_res);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
+// the cursor at step s of the sweep (the first launch forms it and walks down
+// from T); m: the ancestors' integer weights are scattered too
+static int path_cursor(gh_pf* pf, const PathSweep& sw, int s, unsigned long long* m) {
+  const int T = pf->t;
+  PathArgs a{};
+  a.cur = pf->path_cur;
+  a.ancs = pf->est_ancs;
+  a.res_before = pf->res_hist;
+  a.anc_pending = pf->cap >= T + 1 ? anc_for_step(pf, T + 1) : nullptr;
+  a.logw = pf->logw;
+  a.stats = pf->stats_all;
+  a.dev = pf->dev;
+  a.m = m;
+  a.n = pf->n;
+  a.init = s == sw.t1;
+  a.s_hi = a.init ? T : s + 1;
+  a.s_lo = s;
+  a.live = flags_live(pf);
+  a.qscale = as_f64((uint64_t)(quant_shift((uint64_t)pf->n) + 1023) << 52);
+  const unsigned nb = (unsigned)std::min<int64_t>((pf->n + kBlock - 1) / kBlock, kPathCursorBlocks);
+  hipLaunchKernelGGL(k_path_cursor, dim3(nb), dim3(kBlock), 0, pf->s, a);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
+static EstArgs path_est_args(gh_pf* pf, int s) {
+  EstArgs a{};
+  a.x = slot_x(pf, s);
+  a.anc_pending = pf->path_cur;  // index-array mode: the cursor
+  a.logw = pf->logw;
+  a.stats = pf->stats_all;
+  a.dev = pf->dev;
+  a.n = pf->n;
+  a.t_target = a.t_cur = pf->t;
+  a.live = flags_live(pf);
+  return a;
+}
+
+template <int D>
+static void launch_path_est(gh_pf* pf, const EstArgs& a, unsigned nb, bool cov) {
+  if (cov)
+    hipLaunchKernelGGL((k_est_cov<D, true>), dim3(nb, est_panels(D)), dim3(kBlock), 0, pf->s, a);
+  else
+    hipLaunchKernelGGL((k_est_mean<D, true>), dim3(nb), dim3(kBlock), 0, pf->s, a);
+}
+
+static int path_est_pass(gh_pf* pf, const EstArgs& a, unsigned nb, bool cov) {
+  if (cov) nb = std::min<unsigned>(nb, kEstCovBlocks);
+  switch (pf->D) {
+#define GH_EST_CASE(D) case D: launch_path_est<D>(pf, a, nb, cov); break;
+    GH_EST_CASE(1) GH_EST_CASE(2) GH_EST_CASE(3) GH_EST_CASE(4) GH_EST_CASE(5) GH_EST_CASE(6) GH_EST_CASE(7)
+    GH_EST_CASE(8) GH_EST_CASE(9) GH_EST_CASE(10) GH_EST_CASE(11) GH_EST_CASE(12) GH_EST_CASE(13) GH_EST_CASE(14)
+    GH_EST_CASE(15) GH_EST_CASE(16)
+#undef GH_EST_CASE
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_est_fold, dim3(1), dim3(1024), 0, pf->s, (const double*)pf->est_part, (int)nb, pf->D,
+                     cov ? 1 : 0, a.res);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
+extern "C" int gh_pf_estimate_path(gh_pf* pf, int t0, int t1, double* ess, int64_t* distinct, double* mean,
+                                   double* cov) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  if (!ess && !distinct && !mean && !cov)
+    return set_err(GH_E_INVAL, "gh_pf_estimate_path: ess, distinct, mean and cov are all null");
+  const int D = pf->D;
+  // a step's block: ess, mean[D], cov[D][D], W (k_est_fold's), the bits of distinct
+  const size_t stride = (size_t)est_result_doubles(D > 0 && D <= 16 ? D : 1) + 2;
+  PathSweep sw;
+  CHECK(path_open(pf, "gh_pf_estimate_path", t0, t1, stride, sw));
+  const bool states = mean || cov, diag = ess || distinct;
+  if (states && !pf->est_part)
+    HIP_TRY(hipMalloc(&pf->est_part, sizeof(double) * (size_t)est_entries(D) * sw.nb));
+  const unsigned nbd = (unsigned)std::min<int64_t>((pf->n + kBlock - 1) / kBlock, kPathDiagBlocks);
+  if (diag) {
+    if (!pf->path_m) HIP_TRY(hipMalloc(&pf->path_m, sizeof(unsigned long long) * (size_t)pf->n));
+    if (!pf->path_part) HIP_TRY(hipMalloc(&pf->path_part, sizeof(uint64_t) * 3 * kPathDiagBlocks));
+    HIP_TRY(hipMemsetAsync(pf->path_m, 0, sizeof(unsigned long long) * (size_t)pf->n, pf->s));
+  }
+  for (int s = sw.t1; s >= sw.t0; --s) {
+    double* res = pf->path_res + 1 + stride * (size_t)(s - sw.t0);
+    CHECK(path_cursor(pf, sw, s, diag ? pf->path_m : nullptr));
+    if (diag) {
+      hipLaunchKernelGGL(k_path_diag, dim3(nbd), dim3(kBlock), 0, pf->s, pf->path_m, pf->n, pf->path_part);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_path_diag_fold, dim3(1), dim3(64), 0, pf->s, (const uint64_t*)pf->path_part, (int)nbd, res,
+                         est_result_doubles(D) + 1);
+      HIP_TRY(hipGetLastError());
+    }
+    if (states) {
+      EstArgs a = path_est_args(pf, s);
+      a.part = pf->est_part;
+      a.res = res;
+      CHECK(path_est_pass(pf, a, sw.nb, false));
+      if (cov) CHECK(path_est_pass(pf, a, sw.nb, true));
+    }
+  }
+  std::vector<double> h(1 + stride * (size_t)sw.L);
+  CHECK(d2h(pf, h.data(), pf->path_res, sizeof(double) * h.size()));
+  if (h[0] != h[0])
+    return set_err(GH_E_NUMERIC, "gh_pf_estimate_path: the log-weights are all -inf, or hold a NaN or +inf");
+  for (int i = 0; i < sw.L; ++i) {
+    const double* r = h.data() + 1 + stride * (size_t)i;
+    if (ess) ess[i] = r[0];
+    if (distinct) memcpy(distinct + i, r + est_result_doubles(D) + 1, sizeof(int64_t));
+    if (mean) memcpy(mean + (size_t)i * D, r + 1, sizeof(double) * D);
+    if (cov) memcpy(cov + (size_t)i * D * D, r + 1 + D, sizeof(double) * D * D);
+  }
+  return GH_OK;
+}
+
+template <int D>
+static void launch_path_qt_hist(gh_pf* pf, const QtArgs& a, unsigned nb) {
+  const unsigned chunks = (unsigned)((a.n_probs + qt_chunk_probs(D) - 1) / qt_chunk_probs(D));
+  hipLaunchKernelGGL((k_qt_hist<D, true>), dim3(nb, chunks), dim3(kBlock), 0, pf->s, a);
+}
+
+extern "C" int gh_pf_quantiles_path(gh_pf* pf, int t0, int t1, int n_probs, const double* probs, double* out) {
+  if (!pf) return set_err(GH_E_INVAL, "null pf");
+  if (!out) return set_err(GH_E_INVAL, "gh_pf_quantiles_path: out is null");
+  if (n_probs < 1 || n_probs > kQtMaxProbs)
+    return set_err(GH_E_INVAL, "gh_pf_quantiles_path: %d probabilities outside 1..%d", n_probs, kQtMaxProbs);
+  if (!probs) return set_err(GH_E_INVAL, "gh_pf_quantiles_path: null probs");
+  QtSel sel{};
+  for (int j = 0; j < n_probs; ++j) {
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
+      return set_err(GH_E_INVAL, "gh_pf_quantiles_path: probability %d (%g) outside [0, 1]", j, probs[j]);
+    sel.u[j] = (uint64_t)(probs[j] * 0x1p53);  // exact: a scaling by a power of two, then the floor
+  }
+  const int D = pf->D;
+  const int pairs = n_probs * D;
+  const size_t stride = 1 + (size_t)(pairs > 0 ? pairs : 1);  // a step's block: k_qt_select's marker, out[pairs]
+  PathSweep sw;
+  CHECK(path_open(pf, "gh_pf_quantiles_path", t0, t1, stride, sw));
+  if (!pf->qt_buf) HIP_TRY(hipMalloc(&pf->qt_buf, sizeof(uint64_t) * kQtScratchWords));
+  sel.hist = pf->qt_buf;
+  sel.prefix = pf->qt_buf + kQtHistWords;
+  sel.rank = sel.prefix + kQtMaxPairs;
+  sel.ctl = sel.rank + kQtMaxPairs;
+  sel.pairs = pairs;
+  sel.D = D;
+  // (the steps' markers start as 0; the shared one at path_res[0] is k_est_ess's, enqueued before this)
+  HIP_TRY(hipMemsetAsync(pf->path_res + 1, 0, sizeof(double) * stride * (size_t)sw.L, pf->s));
+  QtArgs a{};
+  a.hist = sel.hist;
+  a.prefix = sel.prefix;
+  a.ctl = sel.ctl;
+  a.qscale = as_f64((uint64_t)(quant_shift((uint64_t)pf->n) + 1023) << 52);
+  a.n_probs = n_probs;
+  for (int s = sw.t1; s >= sw.t0; --s) {
+    CHECK(path_cursor(pf, sw, s, nullptr));
+    a.e = path_est_args(pf, s);
+    sel.res = pf->path_res + 1 + stride * (size_t)(s - sw.t0);
+    HIP_TRY(hipMemsetAsync(sel.hist, 0, sizeof(uint64_t) * (size_t)pairs * kQtBins, pf->s));
+    for (int pass = 0; pass < kQtPasses; ++pass) {
+      a.pass = sel.pass = pass;
+      switch (D) {
+#define GH_QT_CASE(D) case D: launch_path_qt_hist<D>(pf, a, sw.nb); break;
+        GH_QT_CASE(1) GH_QT_CASE(2) GH_QT_CASE(3) GH_QT_CASE(4) GH_QT_CASE(5) GH_QT_CASE(6) GH_QT_CASE(7) GH_QT_CASE(8)
+        GH_QT_CASE(9) GH_QT_CASE(10) GH_QT_CASE(11) GH_QT_CASE(12) GH_QT_CASE(13) GH_QT_CASE(14) GH_QT_CASE(15)
+        GH_QT_CASE(16)
+#undef GH_QT_CASE
+      }
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_qt_select, dim3(1), dim3(1024), 0, pf->s, sel);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  std::vector<double> h(1 + stride * (size_t)sw.L);
+  CHECK(d2h(pf, h.data(), pf->path_res, sizeof(double) * h.size()));
+  bool bad = h[0] != h[0];
+  for (int i = 0; i < sw.L; ++i) bad = bad || h[1 + stride * (size_t)i] != h[1 + stride * (size_t)i];
+  if (bad)
+    return set_err(GH_E_NUMERIC, "gh_pf_quantiles_path: the log-weights are all -inf, or hold a NaN or +inf");
+  for (int i = 0; i < sw.L; ++i) memcpy(out + (size_t)i * pairs, h.data() + 2 + stride * (size_t)i, sizeof(double) * pairs);
   return GH_OK;
 }
 

@@ -1,0 +1,5 @@
+// gh_inst_path.hip — explicit instantiations of the index-array moment and quantile kernels (gh_path.h; see gh_inst.h)
+#include <hip/hip_runtime.h>
+#include "gh_path.h"
+
+GH_PATH_UNIT(template)

@@ -50,7 +50,8 @@ struct EstArgs {
   const double* x;             // wave-tiled states of the target step (xidx)
   const int32_t* const* ancs;  // device array of per-step ancestor arrays (index t-1); read when t_target < t_cur
   const int32_t* res_before;   // res_before[t]: a resample preceded step t
-  const int32_t* anc_pending;  // ancestors of a resample pending after the last step
+  const int32_t* anc_pending;  // ancestors of a resample pending after the last step; index-array mode
+                               // (est_tiles<D, true>): the cursor, a_t(i) of every current particle i
   const double* logw;
   const double* stats;         // the rank's (M, S, S2)
   const DevScalars* dev;
@@ -94,12 +95,16 @@ __device__ __forceinline__ void est_lds_order() {
 // nw: the block's waves (k_forecast launches fewer than kBlock / 64 when its
 // LDS asks for it); an f that takes a third argument gets the lane's particle
 // index, which is past n in the last tile's tail (weight 0, state unspecified).
-template <int D, class F>
+// IDX, the index-array mode (gh_path.h): the genealogy has been walked already
+// and a.anc_pending holds its result, the lane's particle index among a.x's
+// step for every current particle (a pending resample included: it is not
+// applied again); ancs, res_before, t_target and t_cur are not read.
+template <int D, bool IDX = false, class F>
 __device__ __forceinline__ void est_tiles(const EstArgs& a, est_d2* stage, F&& f, const int nw = kBlock / 64) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bool uniform = a.live && (a.dev->pending | a.dev->fire);
-  const bool walk = a.t_target != a.t_cur;
-  const bool gather = walk || (uniform && a.anc_pending);
+  const bool walk = !IDX && a.t_target != a.t_cur;
+  const bool gather = IDX || walk || (uniform && a.anc_pending);
   const double M = a.stats[0];
   const int64_t tiles = (a.n + kTileP - 1) / kTileP;
   for (int64_t tile = (int64_t)blockIdx.x * nw + w; tile < tiles; tile += (int64_t)gridDim.x * nw) {
@@ -118,10 +123,14 @@ __device__ __forceinline__ void est_tiles(const EstArgs& a, est_d2* stage, F&& f
       // (clamped at every hop: a broken record reads a wrong particle, never outside the arrays)
       const auto clamp = [&](int64_t i) { return i < 0 ? 0 : (i >= a.n ? a.n - 1 : i); };
       int64_t idx = in ? j : 0;
-      if (in && uniform && a.anc_pending) idx = clamp(a.anc_pending[idx]);
-      if (in && walk)
-        for (int s = a.t_cur; s > a.t_target; --s)
-          if (a.res_before[s]) idx = clamp(a.ancs[s - 1][idx]);
+      if constexpr (IDX) {
+        if (in) idx = clamp(a.anc_pending[idx]);
+      } else {
+        if (in && uniform && a.anc_pending) idx = clamp(a.anc_pending[idx]);
+        if (in && walk)
+          for (int s = a.t_cur; s > a.t_target; --s)
+            if (a.res_before[s]) idx = clamp(a.ancs[s - 1][idx]);
+      }
 #pragma unroll
       for (int k = 0; k < D; ++k) x[k] = a.x[xidx(idx, k, D)];
     } else if constexpr (state_rows(D)) {
@@ -172,14 +181,15 @@ __device__ __forceinline__ void est_block_partial(const double* acc, double (*re
     part[(int64_t)(e0 + e) * gridDim.x + blockIdx.x] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
 }
 
-template <int D>
+// (IDX: est_tiles' index-array mode, instantiated by gh_inst_path.hip; it always gathers and stages nothing)
+template <int D, bool IDX = false>
 __global__ __launch_bounds__(kBlock) void k_est_mean(EstArgs a) {
-  __shared__ est_d2 stage[state_rows(D) ? (kBlock / 64) * kTileP * D / 2 : 1];
+  __shared__ est_d2 stage[state_rows(D) && !IDX ? (kBlock / 64) * kTileP * D / 2 : 1];
   __shared__ double red[kBlock / 64][D + 1];
   double acc[D + 1];
 #pragma unroll
   for (int e = 0; e <= D; ++e) acc[e] = 0.0;
-  est_tiles<D>(a, stage, [&](double w, const double* x) {
+  est_tiles<D, IDX>(a, stage, [&](double w, const double* x) {
     acc[0] += w;
 #pragma unroll
     for (int k = 0; k < D; ++k) acc[1 + k] = fma(w, w == 0.0 ? 0.0 : x[k], acc[1 + k]);
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void k_est_mean(EstArgs a) {
 
 // One panel of pass 2: entries [PANEL * EP, (PANEL + 1) * EP) of the sums, so
 // that the accumulators stay a register array (D = 16: 152 sums in 3 panels).
-template <int D, int PANEL>
+template <int D, int PANEL, bool IDX>
 __device__ __forceinline__ void est_cov_panel(const EstArgs& a, est_d2* stage) {
   constexpr int E = est_entries(D), P = est_panels(D), EP = (E + P - 1) / P;
   constexpr int E0 = PANEL * EP, E1 = E0 + EP < E ? E0 + EP : E;
@@ -200,7 +210,7 @@ __device__ __forceinline__ void est_cov_panel(const EstArgs& a, est_d2* stage) {
   double acc[EP];
 #pragma unroll
   for (int e = 0; e < EP; ++e) acc[e] = 0.0;
-  est_tiles<D>(a, stage, [&](double w, const double* x) {
+  est_tiles<D, IDX>(a, stage, [&](double w, const double* x) {
     double dx[D], wd[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
@@ -218,15 +228,15 @@ __device__ __forceinline__ void est_cov_panel(const EstArgs& a, est_d2* stage) {
   est_block_partial<E1 - E0>(acc, (double(*)[E1 - E0]) red, a.part, E0);
 }
 
-template <int D>
+template <int D, bool IDX = false>
 __global__ __launch_bounds__(kBlock) void k_est_cov(EstArgs a) {
-  __shared__ est_d2 stage[state_rows(D) ? (kBlock / 64) * kTileP * D / 2 : 1];
+  __shared__ est_d2 stage[state_rows(D) && !IDX ? (kBlock / 64) * kTileP * D / 2 : 1];
   static_assert(est_panels(D) <= 3, "one case per panel");
-  if (blockIdx.y == 0) est_cov_panel<D, 0>(a, stage);
+  if (blockIdx.y == 0) est_cov_panel<D, 0, IDX>(a, stage);
   if constexpr (est_panels(D) > 1)
-    if (blockIdx.y == 1) est_cov_panel<D, 1>(a, stage);
+    if (blockIdx.y == 1) est_cov_panel<D, 1, IDX>(a, stage);
   if constexpr (est_panels(D) > 2)
-    if (blockIdx.y == 2) est_cov_panel<D, 2>(a, stage);
+    if (blockIdx.y == 2) est_cov_panel<D, 2, IDX>(a, stage);
 }
 
 // Fold the nb partial rows in block order (k_fold's style: one 1024-thread

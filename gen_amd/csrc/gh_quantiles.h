@@ -91,10 +91,11 @@ struct QtArgs {
   int n_probs, pass;
 };
 
-template <int D>
+// (IDX: est_tiles' index-array mode, instantiated by gh_inst_path.hip)
+template <int D, bool IDX = false>
 __global__ __launch_bounds__(kBlock) void k_qt_hist(QtArgs a) {
   constexpr int JC = qt_chunk_probs(D);
-  __shared__ est_d2 stage[state_rows(D) ? (kBlock / 64) * kTileP * D / 2 : 1];
+  __shared__ est_d2 stage[state_rows(D) && !IDX ? (kBlock / 64) * kTileP * D / 2 : 1];
   __shared__ unsigned long long bins[JC * D * kQtBins];
   const int lo = 64 - kQtBits * (a.pass + 1);  // the digit's position
   const bool first_pass = a.pass == 0;
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_qt_hist(QtArgs a) {
     // a matching lane adds to the global histogram itself.
     if (blockIdx.y != 0) return;
     unsigned long long* g = (unsigned long long*)a.hist;
-    est_tiles<D>(a.e, stage, [&](double w, const double* x) {
+    est_tiles<D, IDX>(a.e, stage, [&](double w, const double* x) {
       const uint64_t q = w == w ? f64_to_u52(w * a.qscale) : 0;
       const bool live = q != 0;
       if (!__builtin_amdgcn_ballot_w64(live)) return;
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_qt_hist(QtArgs a) {
   const int nj = first_pass ? 1 : (a.n_probs - j0 < JC ? a.n_probs - j0 : JC);
   for (int i = threadIdx.x; i < JC * D * kQtBins; i += kBlock) bins[i] = 0;
   lds_barrier();
-  est_tiles<D>(a.e, stage, [&](double w, const double* x) {
+  est_tiles<D, IDX>(a.e, stage, [&](double w, const double* x) {
     const uint64_t q = w == w ? f64_to_u52(w * a.qscale) : 0;
     const bool live = q != 0;
     if (!__builtin_amdgcn_ballot_w64(live)) return;

@@ -762,6 +762,114 @@ def credible_interval(state: ParticleFilterState, level: float = 0.9, t: int | N
     return q[0], q[1]
 
 
+class ParticlePathEstimate(NamedTuple):
+    """`estimate_path`'s result, step t0 + i at index i: the genealogy's
+    effective sample size [L], the number of distinct ancestors [L] (int64),
+    the weighted mean [L, d] and the weighted population covariance [L, d, d]
+    (None when not asked for)."""
+    ess: np.ndarray
+    distinct: np.ndarray
+    mean: np.ndarray
+    cov: np.ndarray | None
+
+
+def _path_range(state: ParticleFilterState, t0, t1) -> tuple[int, int]:
+    """The steps t0..t1 (t1 None: the current step), refused here when out of range."""
+    T = state.t
+    if t1 is None:
+        t1 = T
+
+    def step(t):
+        return not isinstance(t, bool) and isinstance(t, (int, np.integer)) and 1 <= int(t) <= T
+
+    if not step(t0) or not step(t1) or int(t0) > int(t1):
+        raise _lib.GenHipError(1, f"steps {t0!r}..{t1!r} outside 1..{T} or empty (t1=None: the current step)")
+    return int(t0), int(t1)
+
+
+def _path_probs(probs) -> np.ndarray:
+    try:
+        p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError) as e:
+        raise _lib.GenHipError(1, f"probs {probs!r}: not a sequence of floats") from e
+    if not 1 <= p.size <= 16:
+        raise _lib.GenHipError(1, f"{p.size} probabilities outside 1..16")
+    if not ((p >= 0.0) & (p <= 1.0)).all():
+        raise _lib.GenHipError(1, f"probabilities {probs!r} outside [0, 1]")
+    return p
+
+
+def estimate_path(state: ParticleFilterState, t0: int = 1, t1: int | None = None,
+                  cov: bool = True) -> ParticlePathEstimate:
+    """`estimate(state, t)`'s mean and covariance for every step t = t0..t1
+    (t1 default: the current step T) in one backward walk of the genealogy
+    (gh_pf_estimate_path), bit for bit what the per-step calls return, with one
+    synchronise instead of one per step and n (T - 1) ancestor hops instead of
+    n T (T - 1) / 2 per pass.  Row i is step t0 + i.
+
+    Two diagnostics say how much of the genealogy stands behind each step.
+    With a_t(i) the index among step t's particles of the ancestor of current
+    particle i (through a pending resample first, then one hop per step that a
+    resample preceded, as `states(t)` follows it), q_i `quantiles`' integer
+    weight (floor(exp(lw_i - max lw) 2^shift); 2^shift each while a resample
+    is pending), S = sum q_i and m_t(j) = sum of q_i over the i with a_t(i) = j:
+    distinct[t] = #{j : m_t(j) > 0}, the step-t particles that still have a
+    weighted descendant, and ess[t] = S^2 / sum_j m_t(j)^2, the effective sample
+    size of the step-t marginal that the genealogy carries.  The genealogy
+    coalesces going back, so distinct is non-decreasing in t and ess[t] <=
+    distinct[t]; at the current step without a pending resample distinct is the
+    number of particles with q_i > 0.  Use them to judge the smoothed path:
+    where distinct[t] has fallen to a handful, mean[t], cov[t] and the
+    quantiles of step t are statements about that handful of values, however
+    many particles the filter runs.  Both are the same bits on every call.
+
+    A range that reaches below T needs record_history.  cov=False skips the
+    second pass over each step's states.  The filter is only read.  One rank
+    only."""
+    a, b = _path_range(state, t0, t1)
+    L, d = b - a + 1, state.model.d
+    ess = np.empty(L, dtype=np.float64)
+    distinct = np.empty(L, dtype=np.int64)
+    mean = np.empty((L, d), dtype=np.float64)
+    c = np.empty((L, d, d), dtype=np.float64) if cov else None
+    _lib.check(_lib.load().gh_pf_estimate_path(state.h, a, b, _lib.dptr(ess),
+                                               distinct.ctypes.data_as(ctypes.POINTER(c_int64)), _lib.dptr(mean),
+                                               _lib.dptr(c)))
+    return ParticlePathEstimate(ess, distinct, mean, c)
+
+
+def quantiles_path(state: ParticleFilterState, probs, t0: int = 1, t1: int | None = None) -> np.ndarray:
+    """`quantiles(state, probs, t)` for every step t = t0..t1 (t1 default: the
+    current step) in one backward walk of the genealogy (gh_pf_quantiles_path):
+    shape [L, len(probs), d], row i the bits of `quantiles(state, probs, t0 +
+    i)` — the same integer weights q_i, ranks and total order, read along the
+    same ancestors a_t(i) (`estimate_path` states them).  How many distinct
+    values stand behind step t's quantiles is `estimate_path(...).distinct`.
+    probs: 1..16 floats in [0, 1].  A range that reaches below the current
+    step needs record_history.  The filter is only read.  One rank only."""
+    a, b = _path_range(state, t0, t1)
+    p = _path_probs(probs)
+    out = np.empty((b - a + 1, p.size, state.model.d), dtype=np.float64)
+    _lib.check(_lib.load().gh_pf_quantiles_path(state.h, a, b, int(p.size), _lib.dptr(p), _lib.dptr(out)))
+    return out
+
+
+def median_path(state: ParticleFilterState, t0: int = 1, t1: int | None = None) -> np.ndarray:
+    """`quantiles_path(state, [0.5], t0, t1)[:, 0]`: the weighted median [L, d] of every step."""
+    return quantiles_path(state, [0.5], t0, t1)[:, 0]
+
+
+def credible_band(state: ParticleFilterState, level: float = 0.9, t0: int = 1, t1: int | None = None):
+    """The equal-tailed credible band (lo [L, d], hi [L, d]) at `level` in
+    (0, 1] for every step t0..t1: `credible_interval`'s probabilities,
+    `quantiles_path(state, [(1 - level) / 2, (1 + level) / 2], t0, t1)`."""
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.floating)) or not 0.0 < float(level) <= 1.0:
+        raise _lib.GenHipError(1, f"level {level!r} outside (0, 1]")
+    level = float(level)
+    q = quantiles_path(state, [(1.0 - level) / 2.0, (1.0 + level) / 2.0], t0, t1)
+    return q[:, 0], q[:, 1]
+
+
 class ParticleForecast(NamedTuple):
     """`forecast`'s result, horizon k at index k-1: the weighted mean [H, d]
     and population covariance [H, d, d] of x_{T+k}, the same of y_{T+k}

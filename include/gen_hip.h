@@ -20,6 +20,10 @@
  *   gh_pf_quantiles         the weighted median and      src/inference/particle_filter.jl:31-45: the sort
  *                           credible band of get_traces  per component callers run over get_traces with
  *                           under get_log_weights        get_log_weights (normalize_weights, :8-14)
+ *   gh_pf_estimate_path /
+ *   gh_pf_quantiles_path    the same expectation and the src/inference/particle_filter.jl:31-45, for
+ *                           same sort, for every step    every step of the Unfold: the loop callers run
+ *                           of get_traces at once        over the steps of get_traces with get_log_weights
  *   gh_pf_forecast          particle_filter_step! with   src/inference/particle_filter.jl:139-160 on a
  *                           EmptyChoiceMap() on a copy   copy of the state; the Unfold extended by
  *                           of the state, k = 1..H, and  update with no constraints
@@ -468,6 +472,56 @@ int gh_pf_estimate(gh_pf* pf, int t, double* ess /* 1 */, double* mean /* [d] */
    and continues bit for bit.  Every model family. */
 int gh_pf_quantiles(gh_pf* pf, int t, int n_probs, const double* probs /* [n_probs] */,
                     double* out /* [n_probs][d] */);
+/* Every step's summary in one backward walk of the genealogy: what
+   gh_pf_estimate and gh_pf_quantiles return for each step of a range, and per
+   step how much of the genealogy still stands behind it.  T calls of
+   gh_pf_estimate walk n T (T - 1) / 2 hops per pass and synchronise T times;
+   these walk n (T - 1) hops once and synchronise once.
+   Range: steps t0..t1 with 1 <= t0 <= t1 <= T, T the current step; t1 = 0
+   means T.  L = t1 - t0 + 1 steps; row i of every output is step t0 + i.  A
+   range that reaches below T needs record_history.
+   Ancestors: a_t(i) is the index, among step t's particles, of the ancestor
+   of current particle i, as gh_pf_get_trajectory, gh_pf_estimate and
+   gh_pf_quantiles follow it: while a resample is pending first through the
+   pending resample's ancestors, then one hop through step s's ancestor array
+   for every s in (t, T] that a resample preceded, clamped into [0, n) at
+   every hop.
+   Integer weights: q_i is gh_pf_quantiles' weight, floor(exp(lw_i - M)
+   2^shift), every q_i = 2^shift while a resample is pending; S = sum q_i.  For
+   particle j of step t, m_t(j) = sum of q_i over the i with a_t(i) = j, an
+   exact unsigned 64-bit sum (S < 2^63).
+   Per-step diagnostics:
+     distinct[t] = #{ j : m_t(j) > 0 }     the step-t particles that still have a weighted
+                                           descendant among the current ones
+     ess[t]      = S^2 / sum_j m_t(j)^2    in doubles: the effective sample size of the step-t
+                                           marginal the genealogy carries
+   The genealogy coalesces going back: distinct is non-decreasing in t,
+   ess[t] <= distinct[t], and at t = T without a pending resample distinct is
+   the number of particles with q_i > 0.  Where distinct[t] has fallen to a
+   handful, mean[t], cov[t] and the quantiles of step t rest on that handful
+   of values, whatever n is: the part of a smoothed path with a small
+   distinct[t] is not to be trusted.  The sum of squares goes over the
+   ancestor slots in a fixed order with no floating-point atomics: two calls
+   return the same bits.
+   Moments: mean[t] and cov[t] have the bits of gh_pf_estimate(pf, t, ...)'s
+   mean and cov (the same weights, the same two-pass algorithm, the same grid
+   and the same order of every sum).  Quantiles: out[t][j][k] has the bits of
+   gh_pf_quantiles(pf, t, n_probs, probs, ...).
+   gh_pf_estimate_path: any of ess, distinct, mean, cov may be NULL; all four
+   NULL, or a NULL pf: GH_E_INVAL before any device work.  gh_pf_quantiles_path:
+   n_probs outside 1..16, a NULL probs or out, a probability that is NaN or
+   outside [0, 1]: GH_E_INVAL before any device work.  Both: before init and
+   on the multi-rank path GH_E_STATE; t0 < 1, t1 > T or t0 > t1 GH_E_INVAL;
+   t0 < T without record_history GH_E_STATE; d outside 1..16 GH_E_INVAL;
+   log-weights all -inf, or holding a NaN or +inf GH_E_NUMERIC.  The filter is
+   only read (t, states, weights, log-ML, history, a pending resample and the
+   move counters stay as they are) and continues bit for bit.  Scratch of two
+   arrays of n words and L result blocks is kept on the filter.  Every model
+   family. */
+int gh_pf_estimate_path(gh_pf* pf, int t0, int t1, double* ess /* [L] */, int64_t* distinct /* [L] */,
+                        double* mean /* [L][d] */, double* cov /* [L][d][d] */);
+int gh_pf_quantiles_path(gh_pf* pf, int t0, int t1, int n_probs, const double* probs /* [n_probs] */,
+                         double* out /* [L][n_probs][d] */);
 /* The posterior predictive of x_{T+k} and y_{T+k}, k = 1..horizon, given the
    data up to the current step T, reduced on the device; the filter is only
    read (t, states, weights, log-ML, history, a pending resample and the move
