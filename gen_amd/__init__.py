@@ -50,6 +50,9 @@ from .pf import (
     credible_band,
     ParticleForecast,
     forecast,
+    SmoothedTrajectories,
+    smooth,
+    backward_weights,
     gaussian_drift,
     GaussianDriftProposal,
     mh,
@@ -79,4 +82,5 @@ __all__ = [
     "quantiles", "weighted_median", "credible_interval",
     "ParticlePathEstimate", "estimate_path", "quantiles_path", "median_path", "credible_band",
     "ParticleForecast", "forecast",
+    "SmoothedTrajectories", "smooth", "backward_weights",
 ]

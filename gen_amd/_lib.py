@@ -64,7 +64,8 @@ class PFOpts(ctypes.Structure):
         ("history_capacity", c_int32),
         ("block_size", c_int32),
         ("time_kernels", c_int32),
-        ("reserved", c_int32 * 3),
+        ("record_weights", c_int32),
+        ("reserved", c_int32 * 2),
     ]
 
 
@@ -108,6 +109,9 @@ SIGNATURES = {
     "gh_pf_quantiles_path": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     "gh_pf_forecast": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double),
                                POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "gh_pf_get_log_weights_at": (c_int, [c_void_p, c_int, POINTER(c_double)]),
+    "gh_pf_backward_weights": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double)]),
+    "gh_pf_smooth": (c_int, [c_void_p, c_int, c_int64, c_uint64, POINTER(c_double), POINTER(c_int32)]),
     "gh_pf_sample_unweighted": (c_int, [c_void_p, c_int64, c_uint64, POINTER(c_int64)]),
     "gh_pf_rejuvenate": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
     "gh_pf_mh_select": (c_int, [c_void_p, ctypes.c_uint32, c_int, POINTER(c_int64)]),

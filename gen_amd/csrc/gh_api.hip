@@ -34,6 +34,7 @@
 #include "gh_quantiles.h"
 #include "gh_path.h"
 #include "gh_forecast.h"
+#include "gh_smooth.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
 
@@ -79,6 +80,13 @@ GH_FC_UNIT3(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT4(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT5(GH_EXTERN_TEMPLATE)
 GH_FC_UNIT6(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT0(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT1(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT2(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT3(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT4(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT5(GH_EXTERN_TEMPLATE)
+GH_BS_UNIT6(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1387,6 +1395,21 @@ struct gh_pf {
   StepObs* fc_obs = nullptr;
   int fc_cap = 0;                 // horizons fc_res and fc_obs hold
   size_t fc_part_cap = 0;         // doubles of fc_part
+  // the weight history (record_weights): lwh[t-1] = the log-weights as step t
+  // left them, the vector that pairs with slot t's rows; allocated with the
+  // history chunks
+  std::vector<double*> lwh;
+  bool defer_snapshot = false;    // gh_pf_step_params: the snapshot follows k_add_delta
+  bool params_stepped = false;    // a step under changed parameters was taken (gh_pf_smooth refuses)
+  // gh_pf_smooth's and gh_pf_backward_weights' scratch, allocated at their
+  // first use: the block partials of one group of trajectories (gh_smooth.h),
+  // the output rows and picks (grown with steps x trajectories), one x~ row
+  // and the weights of one step
+  char* sm_buf = nullptr;
+  double* sm_xs = nullptr;
+  int32_t* sm_idx = nullptr;
+  size_t sm_xs_cap = 0, sm_idx_cap = 0;  // doubles of sm_xs, words of sm_idx
+  double* sm_bw = nullptr;        // [16 + n]
   // kernel timing
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -1496,13 +1519,25 @@ static int ensure_capacity(gh_pf* pf, int steps) {
   if (pf->opts.record_history) {
     // allocate the new slots as one chunk (no hipMalloc per step)
     const int add = nc - pf->cap;
-    char* chunk = nullptr;
+    char *chunk = nullptr, *wchunk = nullptr;
     if (hipMalloc(&chunk, (xbytes + abytes) * (size_t)add) != hipSuccess)
       return set_err(GH_E_NOMEM, "history: cannot allocate %d more steps", add);
+    // record_weights: the steps' weight slots, a chunk of their own (the state
+    // slots stay where they were); both chunks exist before either is listed,
+    // so a failure leaves xs, ancs and lwh of one length
+    const size_t wbytes = align_up(sizeof(double) * (size_t)(pf->n ? pf->n : 1));
+    if (pf->opts.record_weights && hipMalloc(&wchunk, wbytes * (size_t)add) != hipSuccess) {
+      hipFree(chunk);
+      return set_err(GH_E_NOMEM, "weight history: cannot allocate %d more steps", add);
+    }
     pf->chunks.push_back(chunk);
     for (int i = 0; i < add; ++i) {
       pf->xs.push_back((double*)(chunk + (xbytes + abytes) * i));
       pf->ancs.push_back((int32_t*)(chunk + (xbytes + abytes) * i + xbytes));
+    }
+    if (wchunk) {
+      pf->chunks.push_back(wchunk);
+      for (int i = 0; i < add; ++i) pf->lwh.push_back((double*)(wchunk + wbytes * i));
     }
   }
   double* ne = nullptr;
@@ -1526,6 +1561,15 @@ static int ensure_capacity(gh_pf* pf, int steps) {
 
 static int32_t* anc_for_step(gh_pf* pf, int t) {  // ancestors consumed by step t
   return pf->opts.record_history ? pf->ancs[t - 1] : pf->ancs[0];
+}
+
+// record_weights: step t's weights into their slot, after everything that
+// writes logw for the step (the step kernel, a conditional filter's pin
+// launches, gh_pf_step_params' k_add_delta) — one device-to-device copy
+static int snapshot_weights(gh_pf* pf, int t) {
+  if (!pf->opts.record_weights || pf->n < 1) return GH_OK;
+  HIP_TRY(hipMemcpyAsync(pf->lwh[t - 1], pf->logw, sizeof(double) * (size_t)pf->n, hipMemcpyDeviceToDevice, pf->s));
+  return GH_OK;
 }
 
 extern "C" void gh_pf_opts_default(gh_pf_opts* o) {
@@ -1560,6 +1604,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->est_res); hipFree(pf->est_part); hipFree(pf->est_ancs); hipFree(pf->qt_buf);
   hipFree(pf->path_cur); hipFree(pf->path_m); hipFree(pf->path_part); hipFree(pf->path_res);
   hipFree(pf->fc_res); hipFree(pf->fc_part); hipFree(pf->fc_obs);
+  hipFree(pf->sm_buf); hipFree(pf->sm_xs); hipFree(pf->sm_idx); hipFree(pf->sm_bw);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
   if (pf->ev_plan) hipEventDestroy(pf->ev_plan);
@@ -2042,6 +2087,11 @@ static int pf_init_impl(gh_model* m, const gh_obs* obs, int proposal, int64_t n_
     delete pf;
     return set_err(GH_E_INVAL, "unknown resampler %d", r);
   }
+  if (pf->opts.record_weights && !pf->opts.record_history) {
+    pf->ctx->n_filters--;
+    delete pf;
+    return set_err(GH_E_INVAL, "gh_pf_init: record_weights needs record_history");
+  }
   pf->n_global = n_particles;
   pf->lo = split_lo(n_particles, ctx->rank, ctx->world);
   pf->n = split_lo(n_particles, ctx->rank + 1, ctx->world) - pf->lo;
@@ -2214,6 +2264,8 @@ static int pf_init_impl(gh_model* m, const gh_obs* obs, int proposal, int64_t n_
     pf->pr.over = true;
     pf->peer_ready = true;
   }
+  rc = snapshot_weights(pf, 1);
+  if (rc) return fail(rc);
   pf->t = 1;
   pf->last_obs = o_prior;  // rejuvenation scores under the model (prior form)
   pf->obs_hist.assign(1, o_prior);
@@ -2378,6 +2430,7 @@ static int pf_step_impl(gh_pf* pf, const gh_obs* obs, int proposal, const double
   pf->obs_hist[t - 1] = o_prior;
   log_raw_obs(pf, t, obs);
   pf->rejuv_moves = 0;
+  if (!pf->defer_snapshot) CHECK(snapshot_weights(pf, t));
   return GH_OK;
 }
 
@@ -3797,6 +3850,189 @@ extern "C" int gh_pf_forecast(gh_pf* pf, int horizon, const double* inputs, doub
   return GH_OK;
 }
 
+// ------------------------------------------------ the weight history and backward simulation
+// (gh_smooth.h)  Every step's log-weights are kept when the filter was made
+// with record_weights (snapshot_weights); gh_pf_backward_weights adds the
+// latent score of step t + 1 to those of step t; gh_pf_smooth draws whole
+// trajectories with them.  One rank; the filter is only read.
+extern "C" int gh_pf_get_log_weights_at(gh_pf* pf, int t, double* out) {
+  if (!pf || !out) return set_err(GH_E_INVAL, "gh_pf_get_log_weights_at: null argument");
+  const int T = pf->t;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_get_log_weights_at before init");
+  if (mr(pf->ctx))
+    return set_err(GH_E_STATE, "gh_pf_get_log_weights_at: not for a filter sharded over ranks (the multi-rank path)");
+  if (t < 0 || t > T)
+    return set_err(GH_E_INVAL, "gh_pf_get_log_weights_at: step %d outside 0..%d (0: the current step)", t, T);
+  if (t == 0 || t == T) return gh_pf_get_log_weights(pf, out);
+  if (!pf->opts.record_weights)
+    return set_err(GH_E_STATE, "record_weights is off: only the current step's weights are kept");
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  return d2h(pf, out, pf->lwh[t - 1], sizeof(double) * (size_t)pf->n);
+}
+
+// what gh_pf_backward_weights and gh_pf_smooth (below step T) refuse alike
+static int backward_ready(gh_pf* pf, const char* who) {
+  if (pf->m->family == GH_FAMILY_REGRESSION)
+    return set_err(GH_E_INVAL, "%s: the regression model has no time steps", who);
+  if (!pf->opts.record_weights)
+    return set_err(GH_E_STATE, "%s needs a filter made with record_weights (every step's weights)", who);
+  if (pf->params_stepped)
+    return set_err(GH_E_STATE, "%s: the filter stepped through gh_pf_step_params, its recorded weights were formed "
+                               "under other parameters than the transition density used here", who);
+  if ((int)pf->obs_hist.size() < pf->t || (int)pf->lwh.size() < pf->t)
+    return set_err(GH_E_STATE, "internal: step history");
+  return GH_OK;
+}
+
+extern "C" int gh_pf_backward_weights(gh_pf* pf, int t, const double* x_next, double* out) {
+  if (!pf || !x_next || !out) return set_err(GH_E_INVAL, "gh_pf_backward_weights: null argument");
+  const int T = pf->t, D = pf->D;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_backward_weights before init");
+  if (mr(pf->ctx))
+    return set_err(GH_E_STATE, "gh_pf_backward_weights: not for a filter sharded over ranks (the multi-rank path)");
+  if (t < 1 || t >= T) return set_err(GH_E_INVAL, "gh_pf_backward_weights: step %d outside 1..%d", t, T - 1);
+  CHECK(backward_ready(pf, "gh_pf_backward_weights"));
+  if (pf->n < 1) return set_err(GH_E_STATE, "gh_pf_backward_weights: no particles");
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  if (!pf->sm_bw) HIP_TRY(hipMalloc(&pf->sm_bw, sizeof(double) * (size_t)(16 + pf->n)));
+  HIP_TRY(hipMemcpyAsync(pf->sm_bw, x_next, sizeof(double) * D, hipMemcpyHostToDevice, pf->s));
+  BsArgs a{};
+  a.x = slot_x(pf, t);
+  a.lw = pf->lwh[t - 1];
+  a.xt = pf->sm_bw;
+  a.bw = pf->sm_bw + 16;
+  a.n = pf->n;
+  a.D = D;
+  a.t = (uint32_t)t;
+  const StepObs& o = pf->obs_hist[t];  // step t + 1's
+  const dim3 grid((unsigned)((pf->n + kBlock - 1) / kBlock));
+  CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+    using M = decltype(model);
+    if constexpr (!std::is_same_v<M, RegModel>)
+      hipLaunchKernelGGL(k_bs_weights<M>, grid, dim3(kBlock), 0, pf->s, (const double*)pf->m->dparams, p, o, a);
+  }));
+  HIP_TRY(hipGetLastError());
+  return d2h(pf, out, a.bw, sizeof(double) * (size_t)pf->n);
+}
+
+extern "C" int gh_pf_smooth(gh_pf* pf, int t0, int64_t n_traj, uint64_t seed, double* xs, int32_t* idx) {
+  if (!pf || !xs) return set_err(GH_E_INVAL, "gh_pf_smooth: null argument");
+  if (n_traj < 1 || n_traj > kBsMaxTraj)
+    return set_err(GH_E_INVAL, "gh_pf_smooth: %lld trajectories outside 1..%d", (long long)n_traj, kBsMaxTraj);
+  const int T = pf->t, D = pf->D;
+  if (T < 1) return set_err(GH_E_STATE, "gh_pf_smooth before init");
+  if (mr(pf->ctx)) return set_err(GH_E_STATE, "gh_pf_smooth: not for a filter sharded over ranks (the multi-rank path)");
+  if (t0 < 1 || t0 > T) return set_err(GH_E_INVAL, "gh_pf_smooth: first step %d outside 1..%d", t0, T);
+  if (pf->m->family == GH_FAMILY_REGRESSION)
+    return set_err(GH_E_INVAL, "gh_pf_smooth: the regression model has no time steps");
+  if (pf->params_stepped)
+    return set_err(GH_E_STATE, "gh_pf_smooth: the filter stepped through gh_pf_step_params, its recorded weights were "
+                               "formed under other parameters than the transition density used here");
+  if (t0 < T) CHECK(backward_ready(pf, "gh_pf_smooth"));
+  if (D < 1 || D > 16) return set_err(GH_E_INVAL, "gh_pf_smooth: no kernel for a latent of %d components", D);
+  const int64_t n = pf->n, M = n_traj;
+  if (n < 1) return set_err(GH_E_STATE, "gh_pf_smooth: no particles");
+  HIP_TRY(hipSetDevice(pf->ctx->device));
+  const int L = T - t0 + 1;
+  const int64_t nblk = (n + kBlock - 1) / kBlock;
+  const int G = bs_group(nblk);
+  // scratch: pmax [G + 1][nblk], bsum [G + 1][nblk], B [G + 1], the error word; row G of each is the start's
+  const size_t rows = (size_t)(G + 1) * (size_t)nblk;
+  if (!pf->sm_buf && hipMalloc(&pf->sm_buf, rows * 16 + sizeof(double) * (size_t)(G + 1) + 16) != hipSuccess)
+    return set_err(GH_E_NOMEM, "gh_pf_smooth: block partials of %d trajectories x %lld blocks", G, (long long)nblk);
+  double* const pmax = (double*)pf->sm_buf;
+  uint64_t* const bsum = (uint64_t*)(pmax + rows);
+  double* const Bm = (double*)(bsum + rows);
+  int* const derr = (int*)(Bm + G + 1);
+  const size_t need = (size_t)L * (size_t)M * (size_t)D;
+  if (pf->sm_xs_cap < need) {
+    hipFree(pf->sm_xs);
+    pf->sm_xs = nullptr;
+    pf->sm_xs_cap = 0;
+    if (hipMalloc(&pf->sm_xs, sizeof(double) * need) != hipSuccess)
+      return set_err(GH_E_NOMEM, "gh_pf_smooth: %d steps x %lld trajectories", L, (long long)M);
+    pf->sm_xs_cap = need;
+  }
+  if (idx && pf->sm_idx_cap < (size_t)L * (size_t)M) {
+    hipFree(pf->sm_idx);
+    pf->sm_idx = nullptr;
+    pf->sm_idx_cap = 0;
+    if (hipMalloc(&pf->sm_idx, sizeof(int32_t) * (size_t)L * (size_t)M) != hipSuccess)
+      return set_err(GH_E_NOMEM, "gh_pf_smooth: %d steps x %lld trajectories", L, (long long)M);
+    pf->sm_idx_cap = (size_t)L * (size_t)M;
+  }
+  CHECK(materialize_marks(pf));  // (a pending resample's ancestors, as gh_pf_quantiles reads them)
+  HIP_TRY(hipMemsetAsync(derr, 0, sizeof(int), pf->s));
+  BsArgs base{};
+  base.err = derr;
+  base.dev = pf->dev;
+  base.live = flags_live(pf);
+  base.n = n;
+  base.nblk = (int)nblk;
+  base.D = D;
+  base.seed = seed;
+  base.qscale = as_f64((uint64_t)(quant_shift((uint64_t)n) + 1023) << 52);
+  // the start's maximum and block sums: the same for every trajectory
+  BsArgs st = base;
+  st.x = slot_x(pf, T);
+  st.lw = pf->logw;
+  st.anc = pf->cap >= T + 1 ? anc_for_step(pf, T + 1) : nullptr;
+  st.pmax = pmax + (size_t)G * nblk;
+  st.bsum = bsum + (size_t)G * nblk;
+  st.B = Bm + G;
+  st.t = (uint32_t)T;
+  hipLaunchKernelGGL(k_sm_start_max, dim3((unsigned)nblk), dim3(kBlock), 0, pf->s, st);
+  hipLaunchKernelGGL(k_bs_fold, dim3(1), dim3(kBlock), 0, pf->s, (const double*)st.pmax, (int)nblk, st.B, derr);
+  hipLaunchKernelGGL(k_sm_start_sum, dim3((unsigned)nblk), dim3(kBlock), 0, pf->s, st);
+  HIP_TRY(hipGetLastError());
+  for (int64_t g0 = 0; g0 < M; g0 += G) {
+    const int g = (int)std::min<int64_t>(G, M - g0);
+    const unsigned chunks = (unsigned)((g + kBsChunk - 1) / kBsChunk);
+    st.G = g;
+    st.m0 = g0;
+    st.xo = pf->sm_xs + ((size_t)(T - t0) * M + g0) * D;
+    st.io = idx ? pf->sm_idx + (size_t)(T - t0) * M + g0 : nullptr;
+    hipLaunchKernelGGL(k_sm_start_pick, dim3((unsigned)g), dim3(kBlock), 0, pf->s, st);
+    HIP_TRY(hipGetLastError());
+    for (int t = T - 1; t >= t0; --t) {
+      BsArgs a = base;
+      a.x = slot_x(pf, t);
+      a.lw = pf->lwh[t - 1];
+      a.xt = pf->sm_xs + ((size_t)(t + 1 - t0) * M + g0) * D;
+      a.xo = pf->sm_xs + ((size_t)(t - t0) * M + g0) * D;
+      a.io = idx ? pf->sm_idx + (size_t)(t - t0) * M + g0 : nullptr;
+      a.pmax = pmax;
+      a.bsum = bsum;
+      a.B = Bm;
+      a.G = g;
+      a.m0 = g0;
+      a.t = (uint32_t)t;
+      const StepObs& o = pf->obs_hist[t];  // step t + 1's
+      CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+        using MT = decltype(model);
+        if constexpr (!std::is_same_v<MT, RegModel>) {
+          const double* prm = (const double*)pf->m->dparams;
+          hipLaunchKernelGGL(k_bs_max<MT>, dim3((unsigned)nblk, chunks), dim3(kBlock), 0, pf->s, prm, p, o, a);
+          hipLaunchKernelGGL(k_bs_fold, dim3((unsigned)g), dim3(kBlock), 0, pf->s, (const double*)a.pmax, (int)nblk,
+                             a.B, derr);
+          hipLaunchKernelGGL(k_bs_sum<MT>, dim3((unsigned)nblk, chunks), dim3(kBlock), 0, pf->s, prm, p, o, a);
+          hipLaunchKernelGGL(k_bs_pick<MT>, dim3((unsigned)g), dim3(kBlock), 0, pf->s, prm, p, o, a);
+        }
+      }));
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  int herr = 0;
+  HIP_TRY(hipMemcpyAsync(xs, pf->sm_xs, sizeof(double) * need, hipMemcpyDeviceToHost, pf->s));
+  if (idx)
+    HIP_TRY(hipMemcpyAsync(idx, pf->sm_idx, sizeof(int32_t) * (size_t)L * (size_t)M, hipMemcpyDeviceToHost, pf->s));
+  CHECK(d2h(pf, &herr, derr, sizeof(int)));
+  if (herr)
+    return set_err(GH_E_NUMERIC, "gh_pf_smooth: a step's backward weights hold a NaN or +inf, or are all -inf (no "
+                                 "particle can precede a drawn state)");
+  return GH_OK;
+}
+
 // Trace score columns (gh_scores.h): per particle and step the latent's and
 // the observation's score, and the trace's total (get_score).
 // The trace score columns of every current particle (k_scores: the genealogy
@@ -3973,8 +4209,11 @@ static int step_params_impl(gh_pf* pf, const gh_obs* obs, int proposal, gh_model
   pf->m = nm;
   pf->obs_hist = rebuilt;
   pf->no_max_only = true;  // k_add_delta rewrites full partials of the changed weights
+  pf->defer_snapshot = true;
   rc = pf_step_impl(pf, obs, proposal, pin_ref);
+  pf->defer_snapshot = false;
   pf->no_max_only = false;
+  if (pf->t != T) pf->params_stepped = true;
   if (rc && pf->t == T) {  // no step was taken: the filter keeps its model and history
     pf->m = const_cast<gh_model*>(m_old);
     pf->obs_hist = hist_old;
@@ -3983,6 +4222,7 @@ static int step_params_impl(gh_pf* pf, const gh_obs* obs, int proposal, gh_model
     hipLaunchKernelGGL(k_add_delta, dim3((unsigned)pf->nb_step), dim3(kBlock), 0, pf->s, pf->logw,
                        (const double*)dnew, (const double*)dold, n, pf->pm, pf->ps, pf->ps2);
     if (hipGetLastError() != hipSuccess) rc = set_err(GH_E_HIP, "gh_pf_step_params: launch");
+    if (!rc) rc = snapshot_weights(pf, pf->t);
     pf->nb_part = pf->nb_step;
     pf->last_pairs = false;
     pf->stats_valid = false;

@@ -79,6 +79,7 @@ enum : uint32_t {
   STREAM_IS = 5,         // importance sampling
   STREAM_MH = 6,         // MH proposals / accept tests
   STREAM_SIM = 7,        // simulate(): latents from draw 0, observations from draw kSimObsDraw
+  STREAM_SMOOTH = 8,     // gh_pf_smooth: trajectory m's pick at step t (id = m, step = t, draw 0)
 };
 constexpr uint32_t kSimObsDraw = 32;
 

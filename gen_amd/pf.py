@@ -473,19 +473,21 @@ def _normal_lp(x, mu, sd) -> float:
 
 
 # --------------------------------------------------------------- the API
-def _opts(resampler: str, record_history: bool, history_capacity: int, time_kernels: int) -> _lib.PFOpts:
+def _opts(resampler: str, record_history: bool, history_capacity: int, time_kernels: int,
+          record_weights: bool = False) -> _lib.PFOpts:
     o = _lib.PFOpts()
     _lib.load().gh_pf_opts_default(byref(o))
     o.resampler = {"systematic": _lib.RESAMPLE_SYSTEMATIC, "multinomial": _lib.RESAMPLE_MULTINOMIAL}[resampler]
     o.record_history = int(record_history)
     o.history_capacity = int(history_capacity)
     o.time_kernels = int(time_kernels)
+    o.record_weights = int(record_weights)
     return o
 
 
 def initialize_particle_filter(model: Model, model_args: tuple, observations, *args, seed: int = 0,
                                resampler: str = "systematic", record_history: bool = True,
-                               history_capacity: int = 0, time_kernels: int = 0,
+                               history_capacity: int = 0, time_kernels: int = 0, record_weights: bool = False,
                                ctx: Context | None = None) -> ParticleFilterState:
     """initialize_particle_filter(model, model_args, observations, num_particles)
     initialize_particle_filter(model, model_args, observations, proposal, proposal_args, num_particles)
@@ -495,7 +497,11 @@ def initialize_particle_filter(model: Model, model_args: tuple, observations, *a
     engine defaults to SYSTEMATIC resampling (the north-star setting, the
     lower-variance scheme, and the only one the multi-rank path exchanges).
     Pass resampler="multinomial" for Gen's distribution of parents; both are
-    unbiased, so log-ML estimates agree in expectation, not draw for draw."""
+    unbiased, so log-ML estimates agree in expectation, not draw for draw.
+
+    record_weights=True (needs record_history) also keeps every step's
+    log-weights, one device-to-device copy of n doubles per step: what
+    get_log_weights(state, t), backward_weights and smooth read."""
     proposal_args = ()
     if len(args) == 1:
         proposal, num_particles = None, args[0]
@@ -509,7 +515,7 @@ def initialize_particle_filter(model: Model, model_args: tuple, observations, *a
     mh = ctx.model_handle(model)
     obs, keep = _step_obs(model, 1, observations)
     h = c_void_p()
-    opts = _opts(resampler, record_history, history_capacity, time_kernels)
+    opts = _opts(resampler, record_history, history_capacity, time_kernels, record_weights)
     qa, nq = _qargs(proposal, proposal_args)
     _lib.check(_lib.load().gh_pf_init_q(mh, byref(obs), _proposal_code(proposal),
                                         _lib.dptr(qa) if qa is not None else None, nq, int(num_particles),
@@ -647,9 +653,16 @@ def log_ml_estimate(state: ParticleFilterState) -> float:
     return out.value
 
 
-def get_log_weights(state: ParticleFilterState) -> np.ndarray:
+def get_log_weights(state: ParticleFilterState, t: int | None = None) -> np.ndarray:
+    """get_log_weights (particle_filter.jl:43-45).  With a step t: the
+    log-weights as step t left them, the vector that pairs with states(t)'s
+    rows (gh_pf_get_log_weights_at; an earlier step than the current one needs
+    a filter made with record_weights=True)."""
     out = np.empty(state.n_local, dtype=np.float64)
-    _lib.check(_lib.load().gh_pf_get_log_weights(state.h, _lib.dptr(out)))
+    if t is None:
+        _lib.check(_lib.load().gh_pf_get_log_weights(state.h, _lib.dptr(out)))
+    else:
+        _lib.check(_lib.load().gh_pf_get_log_weights_at(state.h, _estimate_step(state, t), _lib.dptr(out)))
     return out
 
 
@@ -917,6 +930,68 @@ def forecast(state: ParticleFilterState, horizon: int, inputs=None, cov: bool = 
     return ParticleForecast(x_mean, x_cov, y_mean, y_cov, xs, ys)
 
 
+def backward_weights(state: ParticleFilterState, t: int, x_next) -> np.ndarray:
+    """The backward kernel's log-weights at step t (1 <= t < T) for a state
+    x_next of step t + 1 (gh_pf_backward_weights): b_i = get_log_weights(state,
+    t)[i] + logpdf(x_next | states(t)[i]), the recorded weight plus the score
+    of :chain => t + 1 => :x, one fp64 add.  Unnormalised; -inf where the
+    transition is impossible.  What backward simulation, the forward-filter
+    backward-smoother, two-filter smoothing and ancestor sampling weigh step
+    t's particles by.  Needs record_weights=True.  One rank only."""
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+        raise _lib.GenHipError(1, f"step {t!r} is not an integer")
+    x = np.ascontiguousarray(np.asarray(x_next, dtype=np.float64).reshape(-1))
+    if x.size != state.model.d:
+        raise _lib.GenHipError(1, f"x_next has {x.size} components, the latent {state.model.d}")
+    out = np.empty(state.n_local, dtype=np.float64)
+    _lib.check(_lib.load().gh_pf_backward_weights(state.h, int(t), _lib.dptr(x), _lib.dptr(out)))
+    return out
+
+
+class SmoothedTrajectories(NamedTuple):
+    """`smooth`'s result: xs [L, num_samples, d], the draws' states at steps
+    t0..T (row t - t0), and idx [L, num_samples], the particle of that step
+    each state is (xs[l, m] has the bits of states(t0 + l)[idx[l, m]]).  The
+    draws carry equal weight."""
+    xs: np.ndarray
+    idx: np.ndarray
+
+    def mean(self) -> np.ndarray:
+        """The smoothed mean of every step, [L, d]."""
+        return self.xs.mean(axis=1)
+
+    def cov(self) -> np.ndarray:
+        """The smoothed population covariance of every step, [L, d, d]."""
+        c = self.xs - self.xs.mean(axis=1, keepdims=True)
+        return np.einsum("lmi,lmj->lij", c, c) / self.xs.shape[1]
+
+
+def smooth(state: ParticleFilterState, num_samples: int, seed: int = 0, t0: int = 1) -> SmoothedTrajectories:
+    """num_samples draws from the joint smoothing distribution p(x_t0:T |
+    y_1:T) by backward simulation over the filter's history (gh_pf_smooth;
+    FFBSi, Godsill, Doucet & West 2004).  A draw starts from a current
+    particle picked by its weight and goes back a step at a time, picking among
+    ALL n particles of step t by backward_weights(state, t, its state at t +
+    1): its early steps do not rest on the few ancestors the surviving
+    genealogy (get_traces, estimate_path) has left.  Gen has no smoother; this
+    is the loop a caller would write over get_traces and per-step
+    get_log_weights.  The selection is defined on integers (include/gen_hip.h)
+    and keyed by (seed, draw, step): the same call returns the same bits.  The
+    filter is only read.  Needs record_weights=True unless t0 is the current
+    step; num_samples in 1..65536; cost 2 n num_samples transition densities
+    per step.  One rank only; not for the regression model."""
+    for name, v in (("num_samples", num_samples), ("t0", t0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise _lib.GenHipError(1, f"{name} {v!r} is not an integer")
+    M, T, d = int(num_samples), state.t, state.model.d
+    L = max(T - int(t0) + 1, 1)
+    xs = np.empty((L, max(M, 1), d), dtype=np.float64)
+    idx = np.empty((L, max(M, 1)), dtype=np.int32)
+    _lib.check(_lib.load().gh_pf_smooth(state.h, int(t0), M, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.dptr(xs),
+                                        idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return SmoothedTrajectories(xs, idx)
+
+
 def sample_unweighted_traces(state: ParticleFilterState, num_samples: int, seed: int = 0):
     """Indices (and views) of num_samples traces drawn ∝ normalised weights."""
     idx = np.empty(int(num_samples), dtype=np.int64)
@@ -1109,8 +1184,8 @@ def _ref_state(model: Model, x) -> np.ndarray:
 
 def initialize_conditional_particle_filter(model: Model, model_args: tuple, observations, num_particles: int,
                                            reference_x1, seed: int = 0, record_history: bool = True,
-                                           history_capacity: int = 0, ctx: Context | None = None
-                                           ) -> ParticleFilterState:
+                                           history_capacity: int = 0, ctx: Context | None = None,
+                                           record_weights: bool = False) -> ParticleFilterState:
     """conditional_smc's initialisation (examples/pmmh/smc.jl:110-119):
     particle 0 is the distinguished particle, pinned to reference_x1 with
     weight init_score = log p(y_1 | x_1); multinomial resampling."""
@@ -1121,7 +1196,7 @@ def initialize_conditional_particle_filter(model: Model, model_args: tuple, obse
     obs, keep = _step_obs(model, 1, observations)
     ref = _ref_state(model, reference_x1)
     h = c_void_p()
-    opts = _opts("multinomial", record_history, history_capacity, 0)
+    opts = _opts("multinomial", record_history, history_capacity, 0, record_weights)
     _lib.check(_lib.load().gh_pf_init_conditional(mh, byref(obs), int(num_particles), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   byref(opts), _lib.dptr(ref), byref(h)))
     st = ParticleFilterState(ctx, model, h, int(num_particles))

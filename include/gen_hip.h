@@ -29,6 +29,17 @@
  *                           of the state, k = 1..H, and  update with no constraints
  *                           :y drawn as simulate does    (src/modeling_library/unfold/update.jl:54-78);
  *                                                        :y as src/static_ir/simulate.jl:23-34
+ *   gh_pf_get_log_weights_at get_log_weights as it stood  src/inference/particle_filter.jl:43-45 at every
+ *                           after step t                 step: log_weights before maybe_resample! resets
+ *                                                        them (:189-213)
+ *   gh_pf_backward_weights  log_weights of step t plus   src/inference/particle_filter.jl:43-45 and the
+ *                           the score of :x at t + 1     Unfold kernel's :x score
+ *                                                        (src/static_ir/trace.jl:91-129)
+ *   gh_pf_smooth            backward simulation over     Gen has no smoother: a caller would loop over
+ *                           get_traces and the recorded  get_traces and get_log_weights kept per step
+ *                           log_weights (FFBSi)          (src/inference/particle_filter.jl:31-45) and
+ *                                                        draw as categorical does, as
+ *                                                        sample_unweighted_traces (:62-70) does at T
  *   gh_pf_get_scores        get_score / per-choice scores src/static_ir/trace.jl:91-129
  *   gh_pf_sample_unweighted sample_unweighted_traces     src/inference/particle_filter.jl:62-70
  *   gh_pf_rejuvenate        mh(trace, select(x_t)) on    src/inference/mh.jl:14-26 (applied per
@@ -247,7 +258,9 @@ typedef struct {
   int32_t history_capacity; /* steps to preallocate when record_history (0 = grow) */
   int32_t block_size;     /* 0 = default (256) */
   int32_t time_kernels;   /* k > 0: time every k-th step kernel with hipEvents (gh_pf_kernel_time) */
-  int32_t reserved[3];
+  int32_t record_weights; /* 1: keep every step's log-weights too (needs record_history): one device-to-device
+                             copy of n doubles per step; what gh_pf_backward_weights and gh_pf_smooth read */
+  int32_t reserved[2];
 } gh_pf_opts;
 
 /* ---- context ------------------------------------------------------------ */
@@ -552,6 +565,79 @@ int gh_pf_forecast(gh_pf* pf, int horizon, const double* inputs /* [horizon][d] 
                    double* x_mean /* [H][d] */, double* x_cov /* [H][d][d] */,
                    double* y_mean /* [H][dy] */, double* y_cov /* [H][dy][dy] */,
                    double* xs /* [H][d][n_local] */, double* ys /* [H][dy][n_local] */);
+/* The log-weights as step t left them (1 <= t <= T, T the current step): the
+   vector that pairs with the rows of step t's states, before any resample that
+   followed.  t = 0 or t = T: the current weights, as gh_pf_get_log_weights
+   (zeros while a resample is pending).  An earlier step needs a filter made
+   with gh_pf_opts.record_weights (GH_E_STATE otherwise); with it, init and
+   every step end in one device-to-device copy of the n log-weights into the
+   step's slot, enqueued after everything that writes them (the step kernel,
+   a conditional filter's pinning, gh_pf_step_params' re-scoring).  The moves
+   (gh_pf_rejuvenate, gh_pf_mh_select, ...) rewrite the step's rows and leave
+   its weights alone, so the pairing holds.  With the option off nothing is
+   launched, copied or allocated for it.  NULL pf or host_out, t outside 0..T:
+   GH_E_INVAL; before init and on the multi-rank path: GH_E_STATE. */
+int gh_pf_get_log_weights_at(gh_pf* pf, int t, double* host_out /* n_local */);
+/* The backward kernel's log-weights at step t, 1 <= t < T, for a state x_next
+   of step t + 1:
+     b_i = lw_t[i] + logpdf(x_{t+1} = x_next | x_t = row i of step t)
+   one fp64 add of the recorded weight (gh_pf_get_log_weights_at) and the
+   latent score of step t + 1, the model's own transition density exactly as
+   gh_pf_get_scores evaluates it (per-step inputs and the switching pair
+   included): the weights of backward simulation, of the forward-filter
+   backward-smoother's marginals, of two-filter smoothing and of ancestor
+   sampling.  Unnormalised; -inf where the transition is impossible.  NULL
+   argument, t outside 1..T-1, the regression family: GH_E_INVAL; before init,
+   on the multi-rank path, without record_weights, or after a
+   gh_pf_step_params (the recorded weights were formed under other parameters
+   than the density used here): GH_E_STATE. */
+int gh_pf_backward_weights(gh_pf* pf, int t, const double* x_next /* [d] */, double* host_out /* [n] */);
+/* n_traj draws from the joint smoothing distribution p(x_t0:T | y_1:T) by
+   backward simulation (FFBSi: Godsill, Doucet & West 2004) over the filter's
+   recorded states and weights.  Unlike the surviving genealogy
+   (gh_pf_get_trajectory, gh_pf_estimate_path), whose early steps rest on a
+   handful of ancestors, every step of a draw is picked among all n particles
+   of that step.  The draws carry equal weight; the filter is only read (t,
+   states, weights, log-ML, history, a pending resample and the move counters
+   stay as they are) and continues bit for bit.
+   Definition (it fixes every bit).  For trajectory m and step t the uniform is
+     u = u53(w.x, w.y) 2^53,  w = Philox4x32-10(counter = (m lo, m hi, t, 8 << 16), key = seed)
+   the engine's counter layout with stream 8 (STREAM_SMOOTH) and draw 0; u is a
+   53-bit integer.  With shift = 62 - ceil(log2 n), at most 52 (the
+   resampler's), a vector b of n log-weights gives
+     B      = max_i b_i
+     q_i    = floor(exp(b_i - B) 2^shift)      an unsigned integer; b_i = -inf: 0
+     S      = sum q_i
+     target = floor(u S / 2^53)                exact integer arithmetic, < S
+     pick   = the first i whose inclusive sum q_0 + ... + q_i exceeds the target
+   Start, step T: b = the current log-weights, the pick i* is a current
+   particle and j_T = i*; while a resample is pending every q_i = 2^shift and
+   j_T = the pending resample's ancestor of i* (the particles and weights of
+   gh_pf_quantiles).  Backward, t = T-1 down to t0: b = the backward weights
+   (gh_pf_backward_weights) of step t for x_next = row j_{t+1} of step t + 1,
+   and j_t = the pick.  Outputs: xs[t - t0][m] = row j_t of step t's states (d
+   doubles, with the particle's bits), idx[t - t0][m] = j_t (idx may be NULL).
+   Step t's states are the particles as step t (and any move after it) left
+   them, the rows gh_pf_get_states returned then, paired with
+   gh_pf_get_log_weights_at(pf, t); not gh_pf_get_trajectory(pf, t)'s, which
+   are the ancestors of the current particles.
+   Integer sums and the fp64 maximum do not depend on their order: the same
+   filter, seed and n_traj give the same bits on every run.
+   A NaN or +inf among the b_i, or B = -inf (no particle of step t can precede
+   the drawn state), at any step of any trajectory: GH_E_NUMERIC, reported
+   after the call's one synchronise.  Refused before any device work: NULL pf
+   or xs, n_traj outside 1..65536, t0 outside 1..T, the regression family:
+   GH_E_INVAL; before init, on the multi-rank path, t0 < T without
+   record_weights, a filter that ever stepped through gh_pf_step_params:
+   GH_E_STATE.  t0 = T (T = 1 included) is the start draw alone and needs no
+   weight history.  Cost: 2 n n_traj transition densities per backward step.
+   Scratch kept on the filter until it is destroyed: the block partials (two
+   words per 256 particles) of one launch's trajectories, 1024 of them up to
+   n = 2^20 and fewer above so that they stay within 64 MiB, but never fewer
+   than 64: from n = 2^24 on the scratch is 4.1 n bytes (272 MiB at n = 2^26),
+   half of one step's recorded weights; never n x n_traj. */
+int gh_pf_smooth(gh_pf* pf, int t0, int64_t n_traj, uint64_t seed, double* xs /* [T-t0+1][n_traj][d] */,
+                 int32_t* idx /* [T-t0+1][n_traj] or NULL */);
 /* The score columns of the current particles' traces (the per-choice score
    fields of static_ir/trace.jl:91-129): total[i] = get_score(trace i), and
    (nullable) per_step[t-1][0][i] / per_step[t-1][1][i] = the scores of the
