@@ -65,7 +65,8 @@ class PFOpts(ctypes.Structure):
         ("block_size", c_int32),
         ("time_kernels", c_int32),
         ("record_weights", c_int32),
-        ("reserved", c_int32 * 2),
+        ("ancestor_sampling", c_int32),
+        ("reserved", c_int32),
     ]
 
 

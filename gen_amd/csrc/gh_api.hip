@@ -35,6 +35,7 @@
 #include "gh_path.h"
 #include "gh_forecast.h"
 #include "gh_smooth.h"
+#include "gh_ancestor.h"
 #include "gh_peer.h"
 #include "gh_rank_ab.h"
 
@@ -87,6 +88,13 @@ GH_BS_UNIT3(GH_EXTERN_TEMPLATE)
 GH_BS_UNIT4(GH_EXTERN_TEMPLATE)
 GH_BS_UNIT5(GH_EXTERN_TEMPLATE)
 GH_BS_UNIT6(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT0(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT1(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT2(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT3(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT4(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT5(GH_EXTERN_TEMPLATE)
+GH_AS_UNIT6(GH_EXTERN_TEMPLATE)
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -112,6 +120,9 @@ static const char* dev_error_msg(int code) {
     case kErrGenealogy:
       return "genealogy walk met a broken record (an ancestor that names no particle or no kept row); this "
              "filter's state is no longer valid";
+    case kErrAncestor:
+      return "ancestor sampling: the backward weights of the distinguished particle's parent hold a NaN or +inf, or "
+             "are all -inf (no particle of the step before can precede the reference state)";
     case kErrPeer:
       return "peer transport: another rank did not publish within the wait bound (gh_ctx_set_peer_timeout); "
              "this filter's state is no longer valid";
@@ -1410,6 +1421,9 @@ struct gh_pf {
   int32_t* sm_idx = nullptr;
   size_t sm_xs_cap = 0, sm_idx_cap = 0;  // doubles of sm_xs, words of sm_idx
   double* sm_bw = nullptr;        // [16 + n]
+  // ancestor sampling's scratch (gh_ancestor.h), allocated by
+  // gh_pf_init_conditional and only with the option: b [n], pmax [nblk], bsum [nblk], B [1]
+  double* as_buf = nullptr;
   // kernel timing
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -1605,6 +1619,7 @@ static void pf_free(gh_pf* pf) {
   hipFree(pf->path_cur); hipFree(pf->path_m); hipFree(pf->path_part); hipFree(pf->path_res);
   hipFree(pf->fc_res); hipFree(pf->fc_part); hipFree(pf->fc_obs);
   hipFree(pf->sm_buf); hipFree(pf->sm_xs); hipFree(pf->sm_idx); hipFree(pf->sm_bw);
+  hipFree(pf->as_buf);
   if (pf->aux) hipStreamDestroy(pf->aux);
   if (pf->ev_tot) hipEventDestroy(pf->ev_tot);
   if (pf->ev_plan) hipEventDestroy(pf->ev_plan);
@@ -1976,6 +1991,45 @@ static int pin_upload(gh_pf* pf, const double* ref) {
   return GH_OK;
 }
 
+// Ancestor sampling (gh_ancestor.h): the distinguished particle's parent for
+// step t, drawn among the particles of step t - 1 under the weights as that
+// step left them and the reference state already at pf->pin.  Enqueued after
+// the resample's own ancestor writes and before the step kernel; the kernels
+// return at once where the device flags say that no resample fired.
+static int ancestor_launch(gh_pf* pf, const StepObs& o, int t) {
+  if (!flags_live(pf) || pf->n < 1 || t < 2) return GH_OK;  // (no maybe_resample since the last step)
+  const int64_t n = pf->n, nblk = (n + kBlock - 1) / kBlock;
+  if (!pf->as_buf) return set_err(GH_E_STATE, "internal: ancestor sampling without its scratch");
+  BsArgs a{};
+  a.x = slot_x(pf, t - 1);
+  a.lw = pf->logw;
+  a.xt = pf->pin;
+  a.bw = pf->as_buf;
+  a.pmax = pf->as_buf + n;
+  a.bsum = (uint64_t*)(a.pmax + nblk);
+  a.B = (double*)(a.bsum + nblk);
+  a.io = anc_for_step(pf, t);
+  a.err = &pf->dev->error;
+  a.dev = pf->dev;
+  a.live = 1;
+  a.n = n;
+  a.nblk = (int)nblk;
+  a.D = pf->D;
+  a.seed = pf->seed;
+  a.t = (uint32_t)(t - 1);
+  a.qscale = as_f64((uint64_t)(quant_shift((uint64_t)n) + 1023) << 52);
+  CHECK(with_model(pf->m, [&](auto model, const auto& p) {
+    using M = decltype(model);
+    if constexpr (!std::is_same_v<M, RegModel>)
+      hipLaunchKernelGGL(k_as_score<M>, dim3((unsigned)nblk), dim3(kBlock), 0, pf->s, (const double*)pf->m->dparams, p,
+                         o, a);
+  }));
+  hipLaunchKernelGGL(k_as_sum, dim3((unsigned)std::min<int64_t>(nblk, kAsSumBlocks)), dim3(kBlock), 0, pf->s, a);
+  hipLaunchKernelGGL(k_as_pick, dim3(1), dim3(kBlock), 0, pf->s, a);
+  HIP_TRY(hipGetLastError());
+  return GH_OK;
+}
+
 static int pf_init_impl(gh_model* m, const gh_obs* obs, int proposal, int64_t n_particles, uint64_t seed,
                         const gh_pf_opts* opts, const double* pin_ref, gh_pf** out,
                         const double* qargs = nullptr, int nq = 0);
@@ -2046,12 +2100,28 @@ extern "C" int gh_pf_init_conditional(gh_model* m, const gh_obs* obs, int64_t n_
     return set_err(GH_E_INVAL, "conditional SMC on R ranks over the peer transport needs a bootstrap with sendrecv "
                                "(the multinomial rows go through the host)");
   if (m->family == GH_FAMILY_REGRESSION) return set_err(GH_E_INVAL, "conditional SMC needs a state-space model");
-  return pf_init_impl(m, obs, GH_PROPOSAL_DEFAULT, n_particles, seed, opts, ref_x1, out);
+  if (opts->ancestor_sampling && mr(m->ctx))
+    return set_err(GH_E_STATE, "gh_pf_init_conditional: ancestor sampling is not for a filter sharded over ranks (the "
+                               "parent is drawn among one rank's particles)");
+  CHECK(pf_init_impl(m, obs, GH_PROPOSAL_DEFAULT, n_particles, seed, opts, ref_x1, out));
+  gh_pf* pf = *out;
+  if (pf->opts.ancestor_sampling && pf->n > 0) {  // b [n], pmax, bsum [nblk], B [1]: no allocation inside a step
+    const int64_t nblk = (pf->n + kBlock - 1) / kBlock;
+    if (hipMalloc(&pf->as_buf, sizeof(double) * (size_t)(pf->n + 2 * nblk + 1)) != hipSuccess) {
+      pf_free(pf);
+      *out = nullptr;
+      return set_err(GH_E_NOMEM, "ancestor sampling: the backward weights of %lld particles", (long long)n_particles);
+    }
+  }
+  return GH_OK;
 }
 
 static int pf_init_impl(gh_model* m, const gh_obs* obs, int proposal, int64_t n_particles, uint64_t seed,
                         const gh_pf_opts* opts, const double* pin_ref, gh_pf** out, const double* qargs, int nq) {
   if (!m || !out) return set_err(GH_E_INVAL, "gh_pf_init: null argument");
+  if (opts && opts->ancestor_sampling && !pin_ref)
+    return set_err(GH_E_INVAL, "gh_pf_init: ancestor_sampling is an option of a conditional filter "
+                               "(gh_pf_init_conditional): only a distinguished particle has a parent to draw");
   double q0[4] = {0, 0, 0, 0};
   bool has_q = false;
   if (proposal != GH_PROPOSAL_LINEAR) CHECK(set_qargs(q0, &has_q, proposal, qargs, nq));
@@ -2409,6 +2479,7 @@ static int pf_step_impl(gh_pf* pf, const gh_obs* obs, int proposal, const double
   a.part = pf->plan_pending && a.mark_mode == 2 ? 1 : 0;
   if (pin_ref) {
     CHECK(pin_upload(pf, pin_ref));
+    if (pf->opts.ancestor_sampling) CHECK(ancestor_launch(pf, o_prior, t));
     CHECK(pin_launch(pf, o, false, true));
   }
   CHECK(timed_step(pf, o, a, false));
@@ -2986,7 +3057,8 @@ extern "C" int gh_pf_maybe_resample(gh_pf* pf, double thr, int* did, double* ess
     return set_err(GH_E_INVAL, "ess_threshold %g < 0: pass NaN for the default N/2, 0 to never resample", thr);
   CHECK(resample_enqueue(pf, thr, did || ess));
   // conditional SMC: the distinguished particle's parent is itself (smc.jl:139);
-  // the ancestor array is only read if the resample fired
+  // the ancestor array is only read if the resample fired (with
+  // opts.ancestor_sampling the next step overwrites this word: ancestor_launch)
   if (pf->cond && !mr(pf->ctx)) HIP_TRY(hipMemsetAsync(anc_for_step(pf, pf->t + 1), 0, sizeof(int32_t), pf->s));
   if (did || ess) {
     // the fused one-rank resample posts its decision to the host mailbox as
@@ -4151,6 +4223,9 @@ extern "C" int gh_pf_step_params_conditional(gh_pf* pf, const gh_obs* obs, gh_mo
   if (!pf || !nm || !ref_xt) return set_err(GH_E_INVAL, "gh_pf_step_params_conditional: null argument");
   if (!pf->cond)
     return set_err(GH_E_STATE, "gh_pf_step_params_conditional on a filter not made by gh_pf_init_conditional");
+  if (pf->opts.ancestor_sampling)
+    return set_err(GH_E_STATE, "gh_pf_step_params_conditional: not with ancestor sampling (the parent's weights would "
+                               "need the re-scored weights of the step before)");
   return step_params_impl(pf, obs, GH_PROPOSAL_DEFAULT, nm, ref_xt);
 }
 

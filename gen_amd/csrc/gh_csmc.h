@@ -9,6 +9,7 @@
 // for the model's own (prior) proposal, whose weight increment is the
 // observation log-density.  The other particles are the ordinary filter
 // (smc.jl:143-147); their multinomial ancestors may pick particle 0.
+// (gh_pf_opts.ancestor_sampling draws particle 0's parent instead: gh_ancestor.h.)
 //
 // The step kernel is left untouched: k_pin_pre saves the distinguished
 // particle's new weight before the step overwrites its old one, k_pin_post

@@ -1,0 +1,5 @@
+// gh_inst_ancestor0.hip — explicit instantiations of the ancestor-sampling score kernel (gh_ancestor.h; see gh_inst.h)
+#include <hip/hip_runtime.h>
+#include "gh_ancestor.h"
+
+GH_AS_UNIT0(template)

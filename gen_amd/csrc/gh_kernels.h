@@ -84,6 +84,7 @@ struct DevScalars {
 constexpr int kErrBarrier = 7;             // GH_E_STATE: a grid barrier timed out (blocks not co-resident)
 constexpr int kErrGenealogy = 7 | 1 << 8;  // GH_E_STATE: a genealogy walk met a broken record
 constexpr int kErrPeer = 7 | 2 << 8;       // GH_E_STATE: another rank never published (bounded wait)
+constexpr int kErrAncestor = 3 | 1 << 8;   // GH_E_NUMERIC: ancestor sampling's weights hold a NaN or +inf, or are all -inf
 
 struct StepArgs {
   const double* xprev;   // wave-tiled states of the previous step (xidx)

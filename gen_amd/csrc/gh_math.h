@@ -80,6 +80,8 @@ enum : uint32_t {
   STREAM_MH = 6,         // MH proposals / accept tests
   STREAM_SIM = 7,        // simulate(): latents from draw 0, observations from draw kSimObsDraw
   STREAM_SMOOTH = 8,     // gh_pf_smooth: trajectory m's pick at step t (id = m, step = t, draw 0)
+  // (9: STREAM_SLICE, gh_slice.h)
+  STREAM_ANCESTOR = 10,  // ancestor sampling: the distinguished particle's parent at step t (id = 0, step = t, draw 0)
 };
 constexpr uint32_t kSimObsDraw = 32;
 

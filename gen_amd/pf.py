@@ -474,7 +474,7 @@ def _normal_lp(x, mu, sd) -> float:
 
 # --------------------------------------------------------------- the API
 def _opts(resampler: str, record_history: bool, history_capacity: int, time_kernels: int,
-          record_weights: bool = False) -> _lib.PFOpts:
+          record_weights: bool = False, ancestor_sampling: bool = False) -> _lib.PFOpts:
     o = _lib.PFOpts()
     _lib.load().gh_pf_opts_default(byref(o))
     o.resampler = {"systematic": _lib.RESAMPLE_SYSTEMATIC, "multinomial": _lib.RESAMPLE_MULTINOMIAL}[resampler]
@@ -482,6 +482,7 @@ def _opts(resampler: str, record_history: bool, history_capacity: int, time_kern
     o.history_capacity = int(history_capacity)
     o.time_kernels = int(time_kernels)
     o.record_weights = int(record_weights)
+    o.ancestor_sampling = int(ancestor_sampling)
     return o
 
 
@@ -1185,10 +1186,20 @@ def _ref_state(model: Model, x) -> np.ndarray:
 def initialize_conditional_particle_filter(model: Model, model_args: tuple, observations, num_particles: int,
                                            reference_x1, seed: int = 0, record_history: bool = True,
                                            history_capacity: int = 0, ctx: Context | None = None,
-                                           record_weights: bool = False) -> ParticleFilterState:
+                                           record_weights: bool = False,
+                                           ancestor_sampling: bool = False) -> ParticleFilterState:
     """conditional_smc's initialisation (examples/pmmh/smc.jl:110-119):
     particle 0 is the distinguished particle, pinned to reference_x1 with
-    weight init_score = log p(y_1 | x_1); multinomial resampling."""
+    weight init_score = log p(y_1 | x_1); multinomial resampling.
+
+    ancestor_sampling=True: smc.jl:136-139 make the distinguished particle its
+    own parent at every step; with the option each conditional step whose
+    resample fired draws that parent among all particles of the step before,
+    with probability proportional to their weight times the transition
+    density into the step's reference state (backward_weights(state, t - 1,
+    reference_xt)): particle Gibbs with ancestor sampling (PGAS; Lindsten,
+    Jordan & Schön, JMLR 2014).  state.parents[0] shows the pick once the
+    step has run.  One rank; not with parameter changes inside the sweep."""
     if tuple(model_args)[:1] not in ((1,), ()):
         raise _lib.GenHipError(1, "the particle filter starts at model_args = (1,)")
     ctx = ctx or default_context()
@@ -1196,7 +1207,7 @@ def initialize_conditional_particle_filter(model: Model, model_args: tuple, obse
     obs, keep = _step_obs(model, 1, observations)
     ref = _ref_state(model, reference_x1)
     h = c_void_p()
-    opts = _opts("multinomial", record_history, history_capacity, 0, record_weights)
+    opts = _opts("multinomial", record_history, history_capacity, 0, record_weights, ancestor_sampling)
     _lib.check(_lib.load().gh_pf_init_conditional(mh, byref(obs), int(num_particles), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   byref(opts), _lib.dptr(ref), byref(h)))
     st = ParticleFilterState(ctx, model, h, int(num_particles))
@@ -1233,14 +1244,21 @@ def conditional_particle_filter_step(state: ParticleFilterState, new_args: tuple
 
 
 def conditional_smc(model: Model, observations_per_step, num_particles: int, reference, seed: int = 0,
-                    ess_threshold: float | None = None, ctx: Context | None = None) -> ParticleFilterState:
+                    ess_threshold: float | None = None, ctx: Context | None = None, record_weights: bool = False,
+                    ancestor_sampling: bool = False) -> ParticleFilterState:
     """conditional_smc(scheme, distinguished_particle) (smc.jl:100-151) with the
-    model's own proposal: the whole sweep, reference = [T, d] trajectory."""
+    model's own proposal: the whole sweep, reference = [T, d] trajectory.
+
+    ancestor_sampling=True draws the distinguished particle's parent at every
+    step whose resample fired instead of smc.jl:136-139's fixed one (PGAS;
+    Lindsten, Jordan & Schön, JMLR 2014; initialize_conditional_particle_filter
+    has the definition)."""
     T = len(observations_per_step)
     ref = np.asarray(reference, dtype=np.float64).reshape(T, -1)
     addr = model.obs_address
     st = initialize_conditional_particle_filter(model, (1,), {addr(1): observations_per_step[0]}, num_particles,
-                                                ref[0], seed=seed, history_capacity=T, ctx=ctx)
+                                                ref[0], seed=seed, history_capacity=T, ctx=ctx,
+                                                record_weights=record_weights, ancestor_sampling=ancestor_sampling)
     for t in range(2, T + 1):
         maybe_resample_async(st, ess_threshold)
         conditional_particle_filter_step(st, (t,), (UnknownChange(),), {addr(t): observations_per_step[t - 1]},
@@ -1256,16 +1274,24 @@ def get_particle(state: ParticleFilterState, index: int) -> np.ndarray:
 
 
 def particle_gibbs(model: Model, observations_per_step, num_particles: int, reference, num_sweeps: int,
-                   seed: int = 0, ess_threshold: float | None = None, ctx: Context | None = None):
+                   seed: int = 0, ess_threshold: float | None = None, ctx: Context | None = None,
+                   ancestor_sampling: bool = False):
     """Particle Gibbs: repeat {conditional_smc; draw a final particle with
     probability proportional to its weight; take its trajectory as the next
     reference}.  Returns the list of references after each sweep and the
-    log-ML estimates of the sweeps."""
+    log-ML estimates of the sweeps.
+
+    With smc.jl:136-139's fixed parent every new reference shares its early
+    steps with the old one unless num_particles grows with T, and the chain
+    does not move there.  ancestor_sampling=True (PGAS; Lindsten, Jordan &
+    Schön, JMLR 2014) redraws the reference's parent at every step whose
+    resample fired, which breaks the reference into pieces: the chain mixes at
+    a handful of particles."""
     refs, lmls = [], []
     ref = np.asarray(reference, dtype=np.float64)
     for k in range(num_sweeps):
         st = conditional_smc(model, observations_per_step, num_particles, ref, seed=seed + 1000003 * k,
-                             ess_threshold=ess_threshold, ctx=ctx)
+                             ess_threshold=ess_threshold, ctx=ctx, ancestor_sampling=ancestor_sampling)
         _, idx = sample_unweighted_traces(st, 1, seed=seed + 1000003 * k + 1)
         ref = get_particle(st, int(idx[0]))
         refs.append(ref)

@@ -60,6 +60,9 @@
  *                           selection) on every particle
  *   gh_pf_init_conditional /
  *   gh_pf_step_conditional  conditional_smc              examples/pmmh/smc.jl:100-151
+ *     with gh_pf_opts       the same sweep, the          smc.jl:136-139 fix that parent (parents[ONE] = ONE);
+ *     .ancestor_sampling    distinguished particle's     the draw is PGAS's (Lindsten, Jordan & Schon 2014),
+ *                           parent drawn                 which Gen does not have
  *   gh_is_run               importance_sampling          src/inference/importance.jl:20-52
  *   gh_pmmh_run             PMMH (mh over a PF-estimated  examples/pmmh/example.jl:20-79,
  *                           likelihood)                   examples/pmmh/pf.jl:14-73
@@ -260,7 +263,9 @@ typedef struct {
   int32_t time_kernels;   /* k > 0: time every k-th step kernel with hipEvents (gh_pf_kernel_time) */
   int32_t record_weights; /* 1: keep every step's log-weights too (needs record_history): one device-to-device
                              copy of n doubles per step; what gh_pf_backward_weights and gh_pf_smooth read */
-  int32_t reserved[2];
+  int32_t ancestor_sampling; /* 1: a conditional filter (gh_pf_init_conditional) draws the distinguished
+                                particle's parent at every step whose resample fired (see gh_pf_step_conditional) */
+  int32_t reserved;
 } gh_pf_opts;
 
 /* ---- context ------------------------------------------------------------ */
@@ -735,7 +740,44 @@ int gh_pf_map_optimize(gh_pf* pf, uint32_t selection, double max_step_size, doub
    ref_xt at each step, its parent always itself, its weight the observation
    log-density of the given state (init_score / forward_score of the model's
    own proposal).  Requires opts->resampler == GH_RESAMPLE_MULTINOMIAL and one
-   rank.  Such a filter steps only with gh_pf_step_conditional. */
+   rank.  Such a filter steps only with gh_pf_step_conditional.
+   Ancestor sampling (opts->ancestor_sampling = 1; particle Gibbs with ancestor
+   sampling, PGAS: Lindsten, Jordan & Schon, JMLR 2014).  smc.jl:136-139 make the
+   distinguished particle its own parent at every step, so a new reference
+   shares its early steps with the old one unless n grows with T.  With the
+   option, at a step t >= 2 whose resample fired (a gh_pf_maybe_resample since
+   step t - 1 that decided to resample) gh_pf_step_conditional draws that
+   parent among all n particles of step t - 1 with probability proportional to
+   exp(b_i),
+     b_i = lw_{t-1}[i] + logpdf(x_t = ref_xt | x_{t-1} = row i of step t - 1)
+   the bits of gh_pf_backward_weights(pf, t - 1, ref_xt) on a filter that also
+   records its weights (the option itself does not need record_weights): the
+   log-weights as step t - 1 left them, which a pending resample does not
+   rewrite, plus the model's own transition density, one fp64 add.  The
+   selection is gh_pf_smooth's integer rule unchanged (B, q_i, S, target and
+   the first inclusive sum that exceeds it) under the uniform
+     u = u53(w.x, w.y) 2^53,  w = Philox4x32-10(counter = (0, 0, t, 10 << 16), key = the filter's seed)
+   stream 10 (STREAM_ANCESTOR), draw 0.  The pick J replaces the 0 in entry 0
+   of the ancestors step t consumes, in stream order after the resample's own
+   writes, so gh_pf_get_parents shows it once the step has run.  Nothing else
+   changes: particle 0's state and weight are ref_xt and the observation
+   log-density, every other particle's parent, state and weight have the bits
+   they have without the option, and gh_pf_get_trajectory, gh_pf_get_scores,
+   the *_path walks and the recorded history follow the new parent through
+   the genealogy they already read.  Where no resample fired the ancestors are
+   not read and particle 0 continues itself as without the option: its parent
+   is then no random variable, which keeps the sweep a valid conditional SMC
+   under an adaptive ESS threshold.  No host synchronisation is added to the
+   step; three launches that read each row of step t - 1 once; scratch of
+   8 n + n / 16 bytes allocated by gh_pf_init_conditional.  With the option
+   off nothing is launched or allocated.
+   A NaN or +inf among the b_i, or B = -inf (no particle can precede ref_xt),
+   raises GH_E_NUMERIC on the device: it is returned by the next call that
+   reads the device status (gh_pf_maybe_resample with an output,
+   gh_pf_log_ml_estimate, ...).  Refused before any device work: the option on
+   gh_pf_init / gh_pf_init_q: GH_E_INVAL; on a multi-rank context: GH_E_STATE;
+   gh_pf_step_params_conditional on a filter with the option: GH_E_STATE (the
+   weights of step t - 1 would have to be the re-scored ones). */
 int gh_pf_init_conditional(gh_model* m, const gh_obs* obs, int64_t n_particles, uint64_t seed,
                            const gh_pf_opts* opts, const double* ref_x1 /* [d] */, gh_pf** out);
 int gh_pf_step_conditional(gh_pf* pf, const gh_obs* obs, const double* ref_xt /* [d] */);
