@@ -122,19 +122,3 @@ static __global__ __launch_bounds__(kBlock) void k_as_pick(BsArgs a) {
 
 // X is `extern template` (declaration) or `template` (definition), as in gh_inst.h
 #define GH_AS_KERNELS(X, M, P) X __global__ void gh::k_as_score<M>(const double*, P, gh::StepObs, gh::BsArgs);
-#define GH_AS_LG(X, D)                                                                            \
-  GH_AS_KERNELS(X, GH_BS_LGM(D, 0), gh::LGParams) GH_AS_KERNELS(X, GH_BS_LGM(D, 1), gh::LGParams) \
-  GH_AS_KERNELS(X, GH_BS_LGM(D, 2), gh::LGParams) GH_AS_KERNELS(X, GH_BS_LGM(D, 3), gh::LGParams)
-#define GH_AS_SL(X, D) \
-  GH_AS_KERNELS(X, GH_BS_SLM(D, false), gh::SlotParams) GH_AS_KERNELS(X, GH_BS_SLM(D, true), gh::SlotParams)
-// the units (gh_inst_ancestor<k>.hip), the models of gh_inst_smooth<k>.hip each
-#define GH_AS_UNIT0(X)                                                                                         \
-  GH_AS_KERNELS(X, gh::HMMModel, gh::HMMParams) GH_AS_KERNELS(X, gh::KitModel, gh::KitParams)                  \
-  GH_AS_LG(X, 1) GH_AS_LG(X, 2) GH_AS_LG(X, 3) GH_AS_LG(X, 4) GH_AS_LG(X, 5) GH_AS_LG(X, 6) GH_AS_LG(X, 7)
-#define GH_AS_UNIT1(X) GH_AS_LG(X, 8) GH_AS_LG(X, 9) GH_AS_LG(X, 10) GH_AS_LG(X, 11)
-#define GH_AS_UNIT2(X) GH_AS_LG(X, 12) GH_AS_LG(X, 13) GH_AS_LG(X, 14)
-#define GH_AS_UNIT3(X) GH_AS_LG(X, 15) GH_AS_LG(X, 16)
-#define GH_AS_UNIT4(X) \
-  GH_AS_SL(X, 1) GH_AS_SL(X, 2) GH_AS_SL(X, 3) GH_AS_SL(X, 4) GH_AS_SL(X, 5) GH_AS_SL(X, 6) GH_AS_SL(X, 7) GH_AS_SL(X, 8)
-#define GH_AS_UNIT5(X) GH_AS_SL(X, 9) GH_AS_SL(X, 10) GH_AS_SL(X, 11) GH_AS_SL(X, 12)
-#define GH_AS_UNIT6(X) GH_AS_SL(X, 13) GH_AS_SL(X, 14) GH_AS_SL(X, 15) GH_AS_SL(X, 16)

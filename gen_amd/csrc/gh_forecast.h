@@ -33,6 +33,7 @@
 #pragma once
 #include "gh_moments.h"
 #include "gh_slots.h"
+#include "gh_shapes.h"
 
 namespace gh {
 
@@ -312,20 +313,3 @@ static __global__ __launch_bounds__(1024) void k_fc_fold(const double* part, int
 #define GH_FC_KERNELS(X, M, P)                                              \
   X __global__ void gh::k_forecast<M, 0>(const double*, P, gh::FcArgs);     \
   X __global__ void gh::k_forecast<M, 1>(const double*, P, gh::FcArgs);
-#define GH_FC_LGM(D, S) gh::LGModel<D, S>
-#define GH_FC_SLM(D, L) gh::SlotModel<D, L>
-#define GH_FC_LG(X, D)                                                                    \
-  GH_FC_KERNELS(X, GH_FC_LGM(D, 0), gh::LGParams) GH_FC_KERNELS(X, GH_FC_LGM(D, 1), gh::LGParams) \
-  GH_FC_KERNELS(X, GH_FC_LGM(D, 2), gh::LGParams) GH_FC_KERNELS(X, GH_FC_LGM(D, 3), gh::LGParams)
-#define GH_FC_SL(X, D) \
-  GH_FC_KERNELS(X, GH_FC_SLM(D, false), gh::SlotParams) GH_FC_KERNELS(X, GH_FC_SLM(D, true), gh::SlotParams)
-// the units (gh_inst_forecast<k>.hip), balanced by kernel size
-#define GH_FC_UNIT0(X) \
-  GH_FC_LG(X, 1) GH_FC_LG(X, 2) GH_FC_LG(X, 3) GH_FC_LG(X, 4) GH_FC_LG(X, 5) GH_FC_LG(X, 6) GH_FC_LG(X, 7)
-#define GH_FC_UNIT1(X) GH_FC_LG(X, 8) GH_FC_LG(X, 9) GH_FC_LG(X, 10) GH_FC_LG(X, 11)
-#define GH_FC_UNIT2(X) GH_FC_LG(X, 12) GH_FC_LG(X, 13) GH_FC_LG(X, 14)
-#define GH_FC_UNIT3(X) GH_FC_LG(X, 15) GH_FC_LG(X, 16)
-#define GH_FC_UNIT4(X) \
-  GH_FC_SL(X, 1) GH_FC_SL(X, 2) GH_FC_SL(X, 3) GH_FC_SL(X, 4) GH_FC_SL(X, 5) GH_FC_SL(X, 6) GH_FC_SL(X, 7) GH_FC_SL(X, 8)
-#define GH_FC_UNIT5(X) GH_FC_SL(X, 9) GH_FC_SL(X, 10) GH_FC_SL(X, 11) GH_FC_SL(X, 12)
-#define GH_FC_UNIT6(X) GH_FC_SL(X, 13) GH_FC_SL(X, 14) GH_FC_SL(X, 15) GH_FC_SL(X, 16)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_ancestor.h"
 
-GH_AS_UNIT2(template)
+GH_BIN_LIGHT_LG2(GH_LG_EACH, GH_AS_KERNELS, template)

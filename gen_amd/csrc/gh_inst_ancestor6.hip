@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_ancestor.h"
 
-GH_AS_UNIT6(template)
+GH_BIN_LIGHT_SL2(GH_SL_EACH, GH_AS_KERNELS, template)

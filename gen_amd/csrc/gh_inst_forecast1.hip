@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_forecast.h"
 
-GH_FC_UNIT1(template)
+GH_BIN_LIGHT_LG1(GH_LG_EACH, GH_FC_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_forecast.h"
 
-GH_FC_UNIT2(template)
+GH_BIN_LIGHT_LG2(GH_LG_EACH, GH_FC_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_forecast.h"
 
-GH_FC_UNIT4(template)
+GH_BIN_LIGHT_SL0(GH_SL_EACH, GH_FC_KERNELS, template)

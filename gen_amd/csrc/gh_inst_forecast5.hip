@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_forecast.h"
 
-GH_FC_UNIT5(template)
+GH_BIN_LIGHT_SL1(GH_SL_EACH, GH_FC_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_inst.h"
 
-GH_GRAD_UNIT4(GH_TEMPLATE)
+GH_BIN_HEAVY4(GH_LG_EACH, GH_GRAD_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_inst.h"
 
-GH_LG_UNIT2(GH_TEMPLATE)
+GH_BIN_HEAVY2(GH_LG_DIM, template)

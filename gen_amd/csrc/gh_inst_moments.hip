@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_moments.h"
 
-GH_EST_UNIT(template)
+GH_FOR_D(GH_EST_KERNELS, template)

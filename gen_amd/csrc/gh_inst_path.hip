@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_path.h"
 
-GH_PATH_UNIT(template)
+GH_FOR_D(GH_PATH_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_quantiles.h"
 
-GH_QT_UNIT(template)
+GH_FOR_D(GH_QT_KERNELS, template)

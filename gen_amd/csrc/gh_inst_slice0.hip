@@ -2,4 +2,6 @@
 #include <hip/hip_runtime.h>
 #include "gh_inst.h"
 
-GH_SLICE_UNIT0(GH_TEMPLATE)
+GH_SLICE_KERNELS(template, gh::KitModel, gh::KitParams)
+GH_SLICE_KERNELS(template, gh::RegModel, gh::RegParams)
+GH_BIN_HEAVY0(GH_LG_EACH, GH_SLICE_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_inst.h"
 
-GH_SLICE_UNIT4(GH_TEMPLATE)
+GH_BIN_HEAVY4(GH_LG_EACH, GH_SLICE_KERNELS, template)

@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_inst.h"
 
-GH_SL_UNIT1(GH_TEMPLATE)
+GH_BIN_SLOTS1(GH_SL_PLAIN, template)

@@ -2,4 +2,6 @@
 #include <hip/hip_runtime.h>
 #include "gh_smooth.h"
 
-GH_BS_UNIT0(template)
+GH_BS_KERNELS(template, gh::HMMModel, gh::HMMParams)
+GH_BS_KERNELS(template, gh::KitModel, gh::KitParams)
+GH_BIN_LIGHT_LG0(GH_LG_EACH, GH_BS_KERNELS, template)

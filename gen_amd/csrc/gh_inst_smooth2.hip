@@ -2,4 +2,4 @@
 #include <hip/hip_runtime.h>
 #include "gh_smooth.h"
 
-GH_BS_UNIT2(template)
+GH_BIN_LIGHT_LG2(GH_LG_EACH, GH_BS_KERNELS, template)

@@ -25,6 +25,7 @@
 // whatever its state holds.  A tile's lanes past n have weight 0.
 #pragma once
 #include "gh_kernels.h"
+#include "gh_shapes.h"
 
 namespace gh {
 
@@ -271,11 +272,7 @@ static __global__ __launch_bounds__(1024) void k_est_fold(const double* part, in
 
 }  // namespace gh
 
+// per dimension (GH_FOR_D of gh_shapes.h); X is `extern template` or `template`, as in gh_inst.h
 #define GH_EST_KERNELS(X, D)                          \
   X __global__ void gh::k_est_mean<D>(gh::EstArgs);   \
   X __global__ void gh::k_est_cov<D>(gh::EstArgs);
-#define GH_EST_UNIT(X)                                                                                          \
-  GH_EST_KERNELS(X, 1) GH_EST_KERNELS(X, 2) GH_EST_KERNELS(X, 3) GH_EST_KERNELS(X, 4) GH_EST_KERNELS(X, 5)     \
-  GH_EST_KERNELS(X, 6) GH_EST_KERNELS(X, 7) GH_EST_KERNELS(X, 8) GH_EST_KERNELS(X, 9) GH_EST_KERNELS(X, 10)    \
-  GH_EST_KERNELS(X, 11) GH_EST_KERNELS(X, 12) GH_EST_KERNELS(X, 13) GH_EST_KERNELS(X, 14) GH_EST_KERNELS(X, 15) \
-  GH_EST_KERNELS(X, 16)

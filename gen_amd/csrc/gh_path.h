@@ -158,8 +158,3 @@ static __global__ __launch_bounds__(64) void k_path_diag_fold(const uint64_t* pa
   X __global__ void gh::k_est_mean<D, true>(gh::EstArgs);   \
   X __global__ void gh::k_est_cov<D, true>(gh::EstArgs);    \
   X __global__ void gh::k_qt_hist<D, true>(gh::QtArgs);
-#define GH_PATH_UNIT(X)                                                                                             \
-  GH_PATH_KERNELS(X, 1) GH_PATH_KERNELS(X, 2) GH_PATH_KERNELS(X, 3) GH_PATH_KERNELS(X, 4) GH_PATH_KERNELS(X, 5)    \
-  GH_PATH_KERNELS(X, 6) GH_PATH_KERNELS(X, 7) GH_PATH_KERNELS(X, 8) GH_PATH_KERNELS(X, 9) GH_PATH_KERNELS(X, 10)   \
-  GH_PATH_KERNELS(X, 11) GH_PATH_KERNELS(X, 12) GH_PATH_KERNELS(X, 13) GH_PATH_KERNELS(X, 14) GH_PATH_KERNELS(X, 15) \
-  GH_PATH_KERNELS(X, 16)

@@ -236,9 +236,5 @@ static __global__ __launch_bounds__(1024) void k_qt_select(QtSel s) {
 
 }  // namespace gh
 
+// per dimension (GH_FOR_D of gh_shapes.h); X is `extern template` or `template`, as in gh_inst.h
 #define GH_QT_KERNELS(X, D) X __global__ void gh::k_qt_hist<D>(gh::QtArgs);
-#define GH_QT_UNIT(X)                                                                                        \
-  GH_QT_KERNELS(X, 1) GH_QT_KERNELS(X, 2) GH_QT_KERNELS(X, 3) GH_QT_KERNELS(X, 4) GH_QT_KERNELS(X, 5)       \
-  GH_QT_KERNELS(X, 6) GH_QT_KERNELS(X, 7) GH_QT_KERNELS(X, 8) GH_QT_KERNELS(X, 9) GH_QT_KERNELS(X, 10)      \
-  GH_QT_KERNELS(X, 11) GH_QT_KERNELS(X, 12) GH_QT_KERNELS(X, 13) GH_QT_KERNELS(X, 14) GH_QT_KERNELS(X, 15)  \
-  GH_QT_KERNELS(X, 16)

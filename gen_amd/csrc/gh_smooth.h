@@ -41,6 +41,7 @@
 #pragma once
 #include "gh_kernels.h"
 #include "gh_slots.h"
+#include "gh_shapes.h"
 
 namespace gh {
 
@@ -367,21 +368,3 @@ static __global__ __launch_bounds__(kBlock) void k_sm_start_pick(BsArgs a) {
   X __global__ void gh::k_bs_sum<M>(const double*, P, gh::StepObs, gh::BsArgs);      \
   X __global__ void gh::k_bs_pick<M>(const double*, P, gh::StepObs, gh::BsArgs);     \
   X __global__ void gh::k_bs_weights<M>(const double*, P, gh::StepObs, gh::BsArgs);
-#define GH_BS_LGM(D, S) gh::LGModel<D, S>
-#define GH_BS_SLM(D, L) gh::SlotModel<D, L>
-#define GH_BS_LG(X, D)                                                                            \
-  GH_BS_KERNELS(X, GH_BS_LGM(D, 0), gh::LGParams) GH_BS_KERNELS(X, GH_BS_LGM(D, 1), gh::LGParams) \
-  GH_BS_KERNELS(X, GH_BS_LGM(D, 2), gh::LGParams) GH_BS_KERNELS(X, GH_BS_LGM(D, 3), gh::LGParams)
-#define GH_BS_SL(X, D) \
-  GH_BS_KERNELS(X, GH_BS_SLM(D, false), gh::SlotParams) GH_BS_KERNELS(X, GH_BS_SLM(D, true), gh::SlotParams)
-// the units (gh_inst_smooth<k>.hip), balanced by kernel size
-#define GH_BS_UNIT0(X)                                                                                         \
-  GH_BS_KERNELS(X, gh::HMMModel, gh::HMMParams) GH_BS_KERNELS(X, gh::KitModel, gh::KitParams)                  \
-  GH_BS_LG(X, 1) GH_BS_LG(X, 2) GH_BS_LG(X, 3) GH_BS_LG(X, 4) GH_BS_LG(X, 5) GH_BS_LG(X, 6) GH_BS_LG(X, 7)
-#define GH_BS_UNIT1(X) GH_BS_LG(X, 8) GH_BS_LG(X, 9) GH_BS_LG(X, 10) GH_BS_LG(X, 11)
-#define GH_BS_UNIT2(X) GH_BS_LG(X, 12) GH_BS_LG(X, 13) GH_BS_LG(X, 14)
-#define GH_BS_UNIT3(X) GH_BS_LG(X, 15) GH_BS_LG(X, 16)
-#define GH_BS_UNIT4(X) \
-  GH_BS_SL(X, 1) GH_BS_SL(X, 2) GH_BS_SL(X, 3) GH_BS_SL(X, 4) GH_BS_SL(X, 5) GH_BS_SL(X, 6) GH_BS_SL(X, 7) GH_BS_SL(X, 8)
-#define GH_BS_UNIT5(X) GH_BS_SL(X, 9) GH_BS_SL(X, 10) GH_BS_SL(X, 11) GH_BS_SL(X, 12)
-#define GH_BS_UNIT6(X) GH_BS_SL(X, 13) GH_BS_SL(X, 14) GH_BS_SL(X, 15) GH_BS_SL(X, 16)

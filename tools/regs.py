@@ -1,6 +1,7 @@
 """Print per-kernel register/occupancy usage of libgen_hip's device code.
 
-python tools/regs.py [substring-filter ...]   (GH_REGS_SRC=gh_inst_lg2.hip: another unit)
+python tools/regs.py [substring-filter ...]   (GH_REGS_SRC=gh_inst_lg2.hip: another unit;
+the dimensions each unit instantiates are the GH_BIN_* macros of gen_amd/csrc/gh_shapes.h)
 """
 import re
 import subprocess
